@@ -85,17 +85,31 @@ def make_stylegan2_step(size, batch, phase, device):
     tr = TR.StyleGAN2Trainer(a, mk(), G, D, g_optim, d_optim, g_ema, device, "/tmp/diagan_bench_sg2", **extra)
     zero = torch.tensor(0.0, device=device)
     tr.r1_loss, tr.path_loss, tr.path_lengths = zero, zero, zero
-    state = dict(i=0)
+    state = dict(i=0, losses={})
 
     def step():
-        tr.train_step(state['i'])
+        state['losses'] = tr.train_step(state['i'])
         state['i'] += 1
+    nets = dict(G=G, D=D, g_ema=g_ema)
+    if phase == 2:
+        nets['D_drs'] = extra['drs_discriminator']
+    step.outputs = lambda: (nets, state['losses'])       # what the iteration hands its caller: the nets and the losses
     return step
 
 
 class NullLog:
     def add_metric(self, *a, **k):
         pass
+
+
+class LastValueLog:
+    """keeps the last value of every metric (device scalars stay on the device: no synchronisation in the step)"""
+
+    def __init__(self):
+        self.values = {}
+
+    def add_metric(self, name, value, group=None, precision=4):
+        self.values[name] = value
 
 
 def build_models(dataset, loss_type, phase, device):
@@ -114,11 +128,11 @@ def build_models(dataset, loss_type, phase, device):
     return netG, netD, netD_drs, optG, optD, optD_drs
 
 
-def make_global_step(netG, netD, netD_drs, optG, optD, optD_drs, batches, n_dis, num_steps, device):
-    """The body of LogTrainer.train's while-loop without logging / checkpoint I/O."""
+def make_global_step(netG, netD, netD_drs, optG, optD, optD_drs, batches, n_dis, num_steps, device, log=None):
+    """The body of LogTrainer.train's while-loop without logging / checkpoint I/O (`log`: where the metrics go)."""
     from diagan.trainer.scheduler import DRS_LRScheduler
     sched = DRS_LRScheduler('linear', [o for o in (optD, optD_drs, optG) if o is not None], num_steps)
-    log = NullLog()
+    log = NullLog() if log is None else log
     state = dict(step=0, cursor=0)
 
     def fetch():
@@ -152,7 +166,41 @@ def make_global_step(netG, netD, netD_drs, optG, optD, optD_drs, batches, n_dis,
         host_part()
 
     step.device_part, step.host_part = device_part, host_part      # --graph replays the first, runs the second
+    nets = {k: n for k, n in (("netG", netG), ("netD", netD), ("netD_drs", netD_drs)) if n is not None}
+    step.outputs = lambda: (nets, getattr(log, "values", {}))      # the updated nets and the last metrics
     return step
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, nets, metrics):
+    """--dump-outputs: the state a caller of the timed step holds after its last call, as DIR/<name>.npy.
+    Per network, every floating tensor of its state_dict (parameters and buffers, state_dict order) flattened into one
+    float32 vector `<net>_state.npy`; when all of them together pass the size budget, each vector is replaced by the same
+    fixed, seeded sample of its positions (`<net>_state_sample.npy`, sorted indices, budget shared in proportion to size).
+    Metrics (losses, D outputs, learning rates) go to `metric_<name>.npy` as float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {}
+    for name, net in nets.items():
+        parts = [t.detach().reshape(-1).float() for t in net.state_dict().values() if t.is_floating_point()]
+        flat[name] = torch.cat(parts).cpu().numpy()
+    metric_arrays = {}
+    for k, v in metrics.items():
+        v = v.detach().double().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        metric_arrays["metric_" + re.sub(r"[^A-Za-z0-9]+", "_", k).strip("_")] = v.astype(np.float64)
+    budget = (DUMP_BYTES - sum(a.nbytes for a in metric_arrays.values()) - (1 << 20)) // 4
+    total = sum(a.size for a in flat.values())
+    for name, a in flat.items():
+        if total <= budget:
+            np.save(os.path.join(out_dir, f"{name}_state.npy"), a)
+        else:
+            k = max(1, budget * a.size // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_state_sample.npy"), a[idx])
+    for name, a in metric_arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def cpu_baseline(dataset, res, loss_type, batch, n_dis, budget_s=25.0):
@@ -524,10 +572,17 @@ def main():
                     help="skip the extra (un-scored) SNGAN-64 conv-block roofline leg of the default sngan32 run")
     ap.add_argument("--graph", action="store_true",
                     help="replay the global step as one hipGraph (launch-bound workloads: dcgan); single GPU only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left the caller (network state, metrics) as "
+                         "DIR/<name>.npy (rank 0; at most 64 MB, a fixed sample of larger states)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.warmup < 0:
+        raise SystemExit("--warmup must be >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
 
@@ -568,7 +623,8 @@ def main():
         pool = 2 * args.n_dis
         batches = [(torch.rand(args.batch_size, 3, res, res, generator=gen) * 2 - 1).to(device) for _ in range(pool)]
         step = make_global_step(netG, netD, netD_drs, optG, optD, optD_drs, batches, args.n_dis,
-                                num_steps=50000 if dataset == 'cifar10' else 75000, device=device)
+                                num_steps=50000 if dataset == 'cifar10' else 75000, device=device,
+                                log=LastValueLog() if args.dump_outputs else None)
 
     from diagan.ops import conv as C
     # Roofline instrumentation: the last warm-up step is bracketed launch by launch to find the dominant
@@ -613,6 +669,8 @@ def main():
     dist.synchronize()
     elapsed = time.perf_counter() - t0
     C.TIMER = None
+    if args.dump_outputs and rank == 0:          # before the un-timed steps below move the state on
+        dump_outputs(args.dump_outputs, *eager_step.outputs())
     host_rows = [(issue_s, issue_cpu_s, len(os.sched_getaffinity(0)))]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)

@@ -227,3 +227,26 @@ def test_color_mnist_front_ends(tmp_path):
                             "--resample_score", "ldrv"])     # a non-negative score: the weights go to the sampler as they are
     assert tr2.train_drs and isinstance(tr2.dataloader.sampler, torch.utils.data.WeightedRandomSampler)
     assert (tmp_path / "cm2" / "checkpoints" / "netD_drs" / "netD_drs_26_steps.pth").exists()
+
+
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_repeat_and_follow_steps(tmp_path):
+    """bench.py --dump-outputs: the same arguments give the same arrays (seeded inputs, deterministic kernels), and
+    --steps really is the number of timed steps: one step more leaves the networks elsewhere."""
+    import json
+    import subprocess
+    dumps = {}
+    for tag, steps in (("a", 2), ("b", 2), ("c", 3)):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no_cpu_baseline",
+               "--no_sngan64_leg", "--no_kernel_timer", "--dump-outputs", str(tmp_path / tag)]
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=800)
+        assert out.returncode == 0, out.stderr[-3000:]
+        assert json.loads(out.stdout.strip().splitlines()[-1])["steps"] == steps
+        dumps[tag] = {p.name: np.load(p) for p in (tmp_path / tag).iterdir()}
+    a, b, c = dumps["a"], dumps["b"], dumps["c"]
+    assert {"netG_state.npy", "netD_state.npy", "metric_errD.npy", "metric_errG.npy"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+        np.testing.assert_array_equal(v, b[k], err_msg=k)
+    assert sorted(c) == sorted(a) and not np.array_equal(a["netG_state.npy"], c["netG_state.npy"])

@@ -310,3 +310,31 @@ def test_bench_refuses_a_world_size_that_differs_from_gpus():
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1"], env=env,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_bench_dump_outputs_writes_state_and_metrics_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every network's floating state as one float32 vector, metrics as float64; above the size
+    budget the same fixed, seeded sample of positions on every call, and the files stay under the budget."""
+    import bench
+    torch.manual_seed(0)
+    nets = {"netG": torch.nn.Sequential(torch.nn.Linear(40, 30), torch.nn.BatchNorm1d(30)),
+            "netD": torch.nn.Linear(30, 1)}
+    metrics = {"errD": torch.tensor(0.25), "D(G(z))": torch.tensor([0.5], dtype=torch.float64), "lr_0": 2e-4}
+    bench.dump_outputs(str(tmp_path / "full"), nets, metrics)
+    got = {p.name: np.load(p) for p in (tmp_path / "full").iterdir()}
+    assert sorted(got) == ["metric_D_G_z.npy", "metric_errD.npy", "metric_lr_0.npy", "netD_state.npy", "netG_state.npy"]
+    expect = torch.cat([t.reshape(-1).float() for t in nets["netG"].state_dict().values() if t.is_floating_point()])
+    np.testing.assert_array_equal(got["netG_state.npy"], expect.numpy())
+    assert got["netG_state.npy"].dtype == np.float32 and got["metric_errD.npy"].dtype == np.float64
+    assert float(got["metric_errD.npy"]) == 0.25 and float(got["metric_lr_0.npy"]) == 2e-4
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", (1 << 20) + 4 * 1000)        # room for 1000 of the 1 300+ state values
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), nets, metrics)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert sorted(a) == sorted(b) and "netG_state_sample.npy" in a and "netD_state_sample.npy" in a
+    assert sum(v.size for k, v in a.items() if k.endswith("_sample.npy")) <= 1000
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+    assert np.isin(a["netG_state_sample.npy"], expect.numpy()).all()

@@ -14,8 +14,8 @@ SIZE = int(G["size"])
 T = lambda k: torch.from_numpy(G[k])
 
 
-def params(shapes, seed, grad=True):
-    sd = O.seeded_state(shapes, seed)
+def params(shapes, seed, grad=True, dtype=torch.float32):
+    sd = {k: v.to(dtype) for k, v in O.seeded_state(shapes, seed).items()}
     for k, v in sd.items():
         if grad and not k.startswith("noises."):
             v.requires_grad_(True)
@@ -74,9 +74,12 @@ def test_r1_second_order():
 
 
 def test_generator_loss_and_path_length_second_order():
-    sg = params(O.generator_shapes(SIZE), int(G["seed_g"]))
-    sdd = params(O.discriminator_shapes(SIZE), int(G["seed_d"]), grad=False)
-    fake, _ = O.generator(sg, SIZE, [T("z1")])
+    # evaluated in float64: the gradient of a noise weight is a sum over every pixel that cancels to a small value, so
+    # in fp32 it moves by 1e-3 with the host CPU's summation order; in float64 it is within 4e-6 of the stored vector
+    f64 = lambda k: T(k).double()
+    sg = params(O.generator_shapes(SIZE), int(G["seed_g"]), dtype=torch.float64)
+    sdd = params(O.discriminator_shapes(SIZE), int(G["seed_d"]), grad=False, dtype=torch.float64)
+    fake, _ = O.generator(sg, SIZE, [f64("z1")])
     loss = O.g_nonsaturating_loss(O.discriminator(sdd, SIZE, fake))
     assert abs(loss.item() - float(G["g_loss"])) < 1e-3 * max(1.0, abs(float(G["g_loss"])))
     loss.backward()
@@ -85,8 +88,8 @@ def test_generator_loss_and_path_length_second_order():
 
     for v in sg.values():
         v.grad = None
-    fake, lat = O.generator(sg, SIZE, [T("zp")])
-    pl, mean_path, lengths = O.g_path_regularize(fake, lat, 0.3, T("pl_noise"))
+    fake, lat = O.generator(sg, SIZE, [f64("zp")])
+    pl, mean_path, lengths = O.g_path_regularize(fake, lat, 0.3, f64("pl_noise"))
     np.testing.assert_allclose(lengths.detach().numpy(), G["path_lengths"], rtol=1e-3)
     assert abs(pl.item() - float(G["path_loss"])) < 1e-3 * abs(float(G["path_loss"]))
     assert abs(mean_path.item() - float(G["mean_path"])) < 1e-5
