@@ -715,6 +715,36 @@ int diagan_any_lt_rows(const float* T, const float* row_add, const float* thr_co
 int diagan_any_lt_cols(const float* T, const float* row_add, const float* thr_col, const float* thr_row, int rows,
                        int cols, int ld, float* out, void* stream);
 
+/* ---- FID in feature space (diagan-pkg/diagan/trainer/fid_utils.py:11-92, fid_score.py:17-75), DESIGN §8e -------------------
+ * float64 throughout; every reduction in a fixed order (bit-identical reruns, no float atomics).  The caller owns all memory.
+ * gemm_f64: C = alpha * op(A) B + beta * C + diag * I, row-major, op(A) = A [M][K] or (trans_a) A^T with A stored [K][M];
+ *   beta == 0 does not read C; trace_part (M == N, else NULL): trace_part[t] = sum of the diagonal of output tile row t,
+ *   cdiv(M, diagan_gemm_f64_tile()) values (reduce them with diagan_sum_f64).  C must not alias A or B.
+ * sum_f64: out[0] = sum x[i] (square: sum x[i]^2).  trace_f64: out[0] = tr S.
+ * sym_f64: S = scale * (S + S^T) / 2 in place.  scale_diag_f64: dst = alpha * src + d * I (src NULL: d * I).
+ * fid_term: out[0] = |mu1 - mu2|^2 + tr S1 + tr S2 (calculate_frechet_distance, fid_utils.py:66-67, without the sqrtm term).
+ * feat_moments: one batch x [N][D] (fp32, or fp64 with x_f64): mask[r] = 1.0 if row r is all finite else 0.0 (fid_utils.py:87-88),
+ *   count[0] = rows kept, mean[D] = their column means (:90); part: diagan_feat_colsum_chunks(N) * D doubles of scratch.
+ * feat_center: xc[r][c] = x[r][c] - mean[c] on kept rows, 0 on dropped ones (the co-moment is then gemm_f64(xc^T xc)).
+ * moments_merge: Chan's parallel update of the running (n_run, mean_run, m2_run) by a batch's (n_b, mean_b, m2_b); counts on
+ *   the device as doubles.  sigma = sym(M2) / (n - 1) (np.cov's ddof = 1) is diagan_sym_f64 with scale 1 / (n - 1). */
+int diagan_gemm_f64(const double* A, const double* B, double* C, int M, int N, int K, int lda, int ldb, int ldc, int trans_a,
+                    double alpha, double beta, double diag, double* trace_part, void* stream);
+int diagan_gemm_f64_tile(void);
+int diagan_sum_f64(const double* x, int64_t n, int square, double* out, void* stream);
+int diagan_trace_f64(const double* S, int D, int ld, double* out, void* stream);
+int diagan_sym_f64(double* S, int D, int ld, double scale, void* stream);
+int diagan_scale_diag_f64(const double* src, double* dst, int D, int ld, double alpha, double d, void* stream);
+int diagan_fid_term(const double* mu1, const double* mu2, const double* S1, const double* S2, int D, int ld, double* out,
+                    void* stream);
+int diagan_feat_colsum_chunks(int N);
+int diagan_feat_moments(const void* x, int x_f64, int N, int D, int ld, double* mask, double* part, double* count, double* mean,
+                        void* stream);
+int diagan_feat_center(const void* x, int x_f64, const double* mask, const double* mean, int N, int D, int ld, double* xc, int ldc,
+                       void* stream);
+int diagan_moments_merge(double* n_run, double* mean_run, double* m2_run, int ld, const double* n_b, const double* mean_b,
+                         const double* m2_b, int ldb, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
