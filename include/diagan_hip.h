@@ -745,6 +745,24 @@ int diagan_feat_center(const void* x, int x_f64, const double* mask, const doubl
 int diagan_moments_merge(double* n_run, double* mean_run, double* m2_run, int ld, const double* n_b, const double* mean_b,
                          const double* m2_b, int ldb, int D, void* stream);
 
+
+/* ---- non-leaking augmentation (stylegan2/non_leaking.py random_apply_affine + apply_color), DESIGN §8f ----------------------
+ * img / out / gout / gimg: NCHW fp32 [B][3][H][W] (this section's tensors are NCHW, not NHWC).  pad_*: get_padding of G^-1 over
+ *   the batch, WITHOUT the filter margin 6; each pad + 6 must be < its image side (the reference's reflect-pad condition).
+ * params: float64 [B][diagan_augment_params()] per sample: X0 Xj Xi Y0 Yj Yi (the warp's bilinear sample point in pixels of the
+ *   2x image, ix = X0 + Xj col + Xi row, iy = Y0 + Yj col + Yi row, for the 2x output pixel (row, col)), C[0..2][0..2] row-major,
+ *   C[0..2][3].
+ * workspace: diagan_augment_workspace(..., backward, &bytes) bytes (the 2x image; twice that for the backward).
+ * forward: out = crop(down(warp(up(reflect_pad(img))))) under C.  backward: gimg = the adjoint applied to gout (G, C constant),
+ *   gather form, fixed summation order (bit-identical reruns, no float atomics).  out / gimg must not alias the input.
+ *   The backward's work per 2x pixel grows as the square of G's zoom (row sums of |G[:2, :2]|); the Python side accepts <= 8. */
+int diagan_augment_params(void);
+int diagan_augment_workspace(int B, int H, int W, int pad_x1, int pad_x2, int pad_y1, int pad_y2, int backward, int64_t* bytes);
+int diagan_augment_forward(const float* img, const double* params, int B, int H, int W, int pad_x1, int pad_x2, int pad_y1,
+                           int pad_y2, float* out, void* workspace, void* stream);
+int diagan_augment_backward(const float* gout, const double* params, int B, int H, int W, int pad_x1, int pad_x2, int pad_y1,
+                            int pad_y2, float* gimg, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,11 +41,11 @@ COMMON = [
     (("--channel_multiplier",), dict(type=int, default=2, help="config-f = 2, else = 1")),
     (("--wandb",), dict(action="store_true", help="accepted for compatibility; not used")),
     (("--local_rank",), dict(type=int, default=0, help="local rank for distributed training")),
-    (("--augment",), dict(action="store_true", help="non leaking augmentation (not part of the accelerated path)")),
-    (("--augment_p",), dict(type=float, default=0)),
+    (("--augment",), dict(action="store_true", help="apply non leaking augmentation")),
+    (("--augment_p",), dict(type=float, default=0, help="probability of applying augmentation. 0 = use adaptive augmentation")),
     (("--ada_target",), dict(type=float, default=0.6)),
     (("--ada_length",), dict(type=int, default=500 * 1000)),
-    (("--ada_every",), dict(type=int, default=256)),
+    (("--ada_every",), dict(type=int, default=256, help="accepted; as in the reference, the update interval is 256")),
     (("--work_dir",), dict(default="./exp_results", type=str, help="output dir")),
     (("--exp_name",), dict(default="test", type=str, help="exp name")),
     (("--seed",), dict(default=1, type=int)),

@@ -145,13 +145,13 @@ class StyleGAN2Trainer:
     """The loop of train_ffhq.py:163-382 and, with `drs_discriminator` set, of train_ffhq_phase2.py:144-400.
 
     `args` carries the reference's flags (iter, start_iter, batch, latent, mixing, r1, d_reg_every, g_reg_every,
-    path_regularize, path_batch_shrink, logit_save_steps, save_logit_after, stop_save_logit_after, n_sample).
-    Adaptive augmentation (non_leaking.py) is not part of this row and `args.augment` must be off."""
+    path_regularize, path_batch_shrink, logit_save_steps, save_logit_after, stop_save_logit_after, n_sample) and, optionally,
+    the augmentation flags (augment, augment_p, ada_target, ada_length).  With `augment`, D sees every real and fake batch
+    through the non-leaking augmentation (non_leaking.py) at probability `ada_aug_p`: fixed at `augment_p` when it is
+    > 0, else tuned by AdaptiveAugment on D's real logits."""
 
     def __init__(self, args, loader, generator, discriminator, g_optim, d_optim, g_ema, device, output_path,
                  drs_loader=None, drs_discriminator=None, drs_d_optim=None, log_every=100, checkpoint_every=5000):
-        if getattr(args, 'augment', False):
-            raise NotImplementedError("adaptive discriminator augmentation is outside the accelerated path")
         self.args, self.device, self.output_path = args, device, Path(output_path)
         self.loader, self.drs_loader = loader, drs_loader
         self.G, self.D, self.g_ema, self.D_drs = generator, discriminator, g_ema, drs_discriminator
@@ -163,6 +163,14 @@ class StyleGAN2Trainer:
         self.accum = 0.5 ** (32 / (10 * 1000))
         self.history = []
         self._iters = {}
+        self.augment = bool(getattr(args, 'augment', False))
+        self.ada_aug_p = args.augment_p if self.augment and args.augment_p > 0 else 0.0
+        self.r_t_stat = 0
+        self.ada = None
+        if self.augment and args.augment_p == 0:
+            from diagan.models.op.augment import AdaptiveAugment
+            # the reference trainers pass the constant 256 here and ignore --ada_every (train_ffhq.py:196); kept
+            self.ada = AdaptiveAugment(args.ada_target, args.ada_length, 256, device)
         if get_world_size() > 1:
             for net in (generator, discriminator, drs_discriminator, g_ema):
                 if net is not None:
@@ -188,9 +196,16 @@ class StyleGAN2Trainer:
         net.sync_grads(optimizer)
         optimizer.step()                                # DDP's gradient averaging: one collective per step
 
-    def _d_update(self, D, optim, real_img, fake_img, regularize, tag, losses):
+    def _aug(self, img):
+        from diagan.models.op.augment import augment
+        return augment(img, self.ada_aug_p)[0]
+
+    def _d_update(self, D, optim, real_img, real_seen, fake_img, regularize, tag, losses):
+        """D step on (real_seen, fake_img) -- the augmented batches with `augment`, else the batches themselves -- and R1 on
+        the un-augmented real_img; returns D's real logits of the D step (before R1)"""
         a = self.args
-        fake_pred, real_pred = D(fake_img), D(real_img)
+        fake_pred, real_pred = D(fake_img), D(real_seen)
+        step_pred = real_pred.detach()                 # what tune() sees: the D-step logits, not the R1 forward below
         d_loss = d_logistic_loss(real_pred, fake_pred)
         losses[tag] = d_loss
         if tag == 'd':
@@ -203,11 +218,14 @@ class StyleGAN2Trainer:
             self._step(D, optim, a.r1 / 2 * r1_loss * a.d_reg_every + 0 * real_pred[0])
             if tag == 'd':
                 self.r1_loss = r1_loss.detach()
+        return step_pred
 
     def _g_update(self, i, losses):
         a = self.args
         noise = mixing_noise(a.batch, a.latent, a.mixing, self.device)
         fake_img, _ = self.G(noise)
+        if self.augment:
+            fake_img = self._aug(fake_img)
         g_loss = g_nonsaturating_loss(self.D(fake_img))
         losses['g'] = g_loss
         self._step(self.G, self.g_optim, g_loss)
@@ -237,8 +255,17 @@ class StyleGAN2Trainer:
             requires_grad(D, True)
         with torch.no_grad():
             fake_img, _ = self.G(mixing_noise(a.batch, a.latent, a.mixing, dev))
-        for D, optim, real, tag in nets_d:
-            self._d_update(D, optim, real, fake_img, i % a.d_reg_every == 0, tag, losses)
+        # augmented in the reference's order (real, drs real, fake: it fixes the CPU random stream); D and D_drs share the fake
+        seen = [self._aug(real) if self.augment else real for _, _, real, _ in nets_d]
+        if self.augment:
+            fake_img = self._aug(fake_img)
+        for (D, optim, real, tag), real_seen in zip(nets_d, seen):
+            real_pred = self._d_update(D, optim, real, real_seen, fake_img, i % a.d_reg_every == 0, tag, losses)
+            if tag == 'd':
+                d_real_pred = real_pred
+        if self.ada is not None:
+            self.ada_aug_p = self.ada.tune(d_real_pred)
+            self.r_t_stat = self.ada.r_t_stat
         requires_grad(self.G, True)
         for D, *_ in nets_d:
             requires_grad(D, False)
@@ -275,8 +302,11 @@ class StyleGAN2Trainer:
                     vals = {k: float(v.detach().mean()) for k, v in reduced.items()}
                     vals['step'] = i
                     self.history.append(vals)
-                    print("; ".join(f"{k}: {vals[k]:.4f}" for k in ('d', 'drs_d', 'g', 'r1', 'path') if k in vals)
-                          + f"; mean path: {self.mean_path_length_avg:.4f}")
+                    line = "; ".join(f"{k}: {vals[k]:.4f}" for k in ('d', 'drs_d', 'g', 'r1', 'path') if k in vals) \
+                        + f"; mean path: {self.mean_path_length_avg:.4f}"
+                    if self.augment:
+                        line += f"; augment: {self.ada_aug_p:.4f}; rt: {self.r_t_stat:.4f}"
+                    print(line)
             if get_rank() == 0 and i > 0 and i % self.checkpoint_every == 0:
                 self.save_checkpoint(i)
         return sample_z
@@ -287,7 +317,7 @@ class StyleGAN2Trainer:
         path.mkdir(parents=True, exist_ok=True)
         ckpt = {"g": self.G.state_dict(), "d": self.D.state_dict(), "g_ema": self.g_ema.state_dict(),
                 "g_optim": self.g_optim.state_dict(), "d_optim": self.d_optim.state_dict(), "args": self.args,
-                "ada_aug_p": 0.0}
+                "ada_aug_p": self.ada_aug_p}
         if self.D_drs is not None:
             ckpt["drs_d"], ckpt["drs_d_optim"] = self.D_drs.state_dict(), self.drs_d_optim.state_dict()
         torch.save(ckpt, path / f"{str(i).zfill(6)}.pt")
