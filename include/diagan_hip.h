@@ -202,6 +202,9 @@ typedef struct diagan_conv_opts {
   int64_t ticket_slots;
 } diagan_conv_opts;
 int diagan_conv_gemm_next_opts(const diagan_conv_opts* opts);
+/* The options pending for the next diagan_conv_gemm call of the calling thread (every field at its default when none are), so that a
+ * caller can add a field to what its own caller set instead of replacing it. */
+int diagan_conv_gemm_pending_opts(diagan_conv_opts* opts);
 /* The tile configuration the last diagan_conv_gemm call of the calling thread resolved to (0: it failed before choosing). */
 int diagan_conv_gemm_last_cfg(void);
 /* The lone-tile implicit-GEMM launches (at most one 64 x 64 output tile per CU, long K loop: the 8x8 maps of SNGAN-32's discriminator;
@@ -236,8 +239,8 @@ int diagan_conv_gemm_x3b_force_form(int form);
  * ask diagan_conv_gemm_final_cfg first).  Use: the four dense parity classes of a stride-2 transposed convolution interleave
  * themselves (mul = 2) instead of being copied into place.  mul = 0 clears a pending map. */
 int diagan_conv_gemm_out_map(int mul, int offy, int offx, int y0, int y1, int x0, int x1, int OH, int OW);
-/* The tile configuration diagan_conv_gemm(tile_cfg = 0) ends up with, including the upgrades to the split-operand kernels (16, 17)
- * that the pick_cfg queries do not model.  plain_epilogue: no backward mask, per-half scales, ReLU on the residual or half-resolution
+/* The tile configuration the next diagan_conv_gemm(tile_cfg = 0) call of the calling thread ends up with, under the options pending for it
+ * (diagan_conv_gemm_next_opts), including the upgrades to the split-operand kernels (16, 17) that the pick_cfg queries do not model.  plain_epilogue: no backward mask, per-half scales, ReLU on the residual or half-resolution
  * residual; want_stats: BatchNorm statistics from the epilogue are requested. */
 int diagan_conv_gemm_final_cfg(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr, int off, int up,
                                int Kp, int allow_split, int64_t ws_floats, int pro_group_rows, int pro_mode, int plain_epilogue,

@@ -1121,6 +1121,7 @@ DIAGAN_API int diagan_conv_gemm(const float* x, const float* w, float* y, const 
                "conv_gemm: tile_cfg 16 (split-operand implicit GEMM) needs stride 1, no up-sampling, Ci %% 32 == 0, an even number of "
                "32-channel K-steps, Kp == R*S*Ci, prologue none / ReLU, no statistics, and %ld floats of workspace", gemm_x3_ws_floats(Co, Kp));
     a.ksplit = 1;
+    g_last_cfg = 16;                        // (the upgrade of a lone-tile pick: report the kernel that runs, as final_cfg does)
     return launch_gemm_x3(a, splitk_ws, st);
   }
   if (cfg == 17) {
@@ -1305,13 +1306,19 @@ DIAGAN_API int diagan_conv_gemm_out_map(int mul, int offy, int offx, int y0, int
   g_map_next = OutMap{mul, offy, offx, y0, y1, x0, x1, OH, OW};
   return DIAGAN_OK;
 }
-// The tile configuration diagan_conv_gemm ends up with for tile_cfg 0, INCLUDING the upgrades to the split-operand kernels
+// The tile configuration the next diagan_conv_gemm call of this thread ends up with for tile_cfg 0 (under the per-call options pending
+// for it), INCLUDING the upgrades to the split-operand kernels
 // (16: conv_gemm_x3.hip, 17: conv_gemm_x3b.hip) that the pick functions do not know: what a caller needs to name the kernel of a
 // launch (kernel timers) or to know whether an output map will be honoured.  plain_epilogue: no mask, no per-half scales, no ReLU on
 // the residual, no half-resolution residual; has_ws: a workspace of ws_floats floats is handed over.
 DIAGAN_API int diagan_conv_gemm_final_cfg(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr,
                                           int off, int up, int Kp, int allow_split, int64_t ws_floats, int pro_group_rows,
                                           int pro_mode, int plain_epilogue, int want_stats) {
+  struct PendingScope {                     // answered under the options the next call of this thread will run with
+    CallOpts saved;
+    PendingScope() : saved(g_opts_now) { g_opts_now = g_opts_next; }
+    ~PendingScope() { g_opts_now = saved; }
+  } pending_scope;
   int cfg = diagan_conv_gemm_pick_cfg_grouped(B, Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up, Kp, allow_split, ws_floats,
                                               pro_group_rows);
   ConvGemmArgs a = {};
@@ -1360,6 +1367,15 @@ DIAGAN_API int diagan_conv_gemm_next_opts(const diagan_conv_opts* o) {
   DG_REQUIRE(!o->tickets || o->ticket_slots > 0, "conv_gemm_next_opts: a ticket buffer needs its slot count");
   g_opts_next = CallOpts{o->wino, o->wino4, o->wino4x, o->gemm_x3, o->gemm_x3b, o->splitk_fused, o->force_ksplit, o->tune, o->tickets,
                          (long)o->ticket_slots};
+  return DIAGAN_OK;
+}
+// the options pending for the next diagan_conv_gemm call of the calling thread (all defaults when none are): a caller that adds a field
+// merges it into what is already pending instead of replacing it
+DIAGAN_API int diagan_conv_gemm_pending_opts(diagan_conv_opts* o) {
+  DG_REQUIRE(o, "conv_gemm_pending_opts: null");
+  const CallOpts& c = g_opts_next;
+  *o = diagan_conv_opts{c.wino, c.wino4, c.wino4x, c.gemm_x3, c.gemm_x3b, c.splitk_fused, c.force_ksplit, c.tune, c.tickets,
+                        (int64_t)c.ticket_slots};
   return DIAGAN_OK;
 }
 // tile configuration the last diagan_conv_gemm call of the calling thread resolved to (0: it failed before choosing)

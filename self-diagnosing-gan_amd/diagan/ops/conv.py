@@ -18,6 +18,7 @@ nat.register("diagan_conv_gemm_set_wino4", [I])
 nat.register("diagan_conv_gemm_set_splitk_fused", [I])
 nat.register("diagan_conv_gemm_set_splitk_tickets", [P, I64])
 nat.register("diagan_conv_gemm_next_opts", [P])
+nat.register("diagan_conv_gemm_pending_opts", [P])
 nat.register("diagan_conv_gemm_last_cfg", [])
 nat.register("diagan_conv_gemm_set_x3", [I])
 nat.register("diagan_conv_gemm_get_x3", [])
@@ -363,6 +364,24 @@ def next_opts(tickets=None, **fields):
     nat.call("diagan_conv_gemm_next_opts", _ct.byref(o))
 
 
+def pending_opts():
+    """the options pending for the next convolution launch of this thread (a ConvOpts; every field at its default when none are)"""
+    o = ConvOpts()
+    nat.call("diagan_conv_gemm_pending_opts", _ct.byref(o))
+    return o
+
+
+def _opts_key(o):
+    return tuple(getattr(o, n) for n, _ in ConvOpts._fields_[:8])
+
+
+def _without_wino(o):
+    """a copy of the options `o` that also keeps the launch off the Winograd kernels"""
+    m = ConvOpts.from_buffer_copy(o)
+    m.wino, m.wino4 = 0, 0
+    return m
+
+
 def last_cfg():
     """tile configuration the last convolution launch of this thread resolved to"""
     return nat.fn("diagan_conv_gemm_last_cfg")()
@@ -437,8 +456,12 @@ def _gemm(x, w, out, geo_params, R, S, Kp, bias, residual, mask_src, mask_slope,
             TIMER.end("conv3x3_ci4_kernel", 2.0 * B * Ho * Wo * Co * R * S * Ci, t0, (B * Ho * Wo, Co, R * S * Ci, "pro0"))
         return out
     ws = _splitk_ws(x.device)
-    if tile_cfg == 0 and not wino:        # caller keeps to the implicit GEMM (the StyleGAN2 autograd ops by default)
-        tile_cfg = nat.fn("diagan_conv_gemm_pick_cfg")(B * Ho * Wo, Co, Kp, 0 if want_stats else 1)
+    if tile_cfg == 0 and not wino:        # caller keeps to the implicit GEMM (the StyleGAN2 autograd ops with DIAGAN_SG2_WINO=0)
+        if want_stats:                    # (the statistics buffer is sized for a fixed tile)
+            tile_cfg = nat.fn("diagan_conv_gemm_pick_cfg")(B * Ho * Wo, Co, Kp, 0)
+        else:                             # the automatic choice without Winograd, its split-operand upgrades included; the launch's options
+            # are ADDED to whatever a caller already set for it (one pending set per thread)
+            nat.call("diagan_conv_gemm_next_opts", _ct.byref(_without_wino(pending_opts())))
     if want_stats:
         # statistics from the epilogue always win over split-K + a separate reduction pass over y (G-32 block2,
         # M=4096: 60 us unsplit with statistics vs 54 + 6 (second stage) + 20 (column reduction) us)
@@ -453,7 +476,7 @@ def _gemm(x, w, out, geo_params, R, S, Kp, bias, residual, mask_src, mask_slope,
     if TIMER is not None and TIMER.wants_any():
         # (cached per call signature: on launch-bound workloads the name lookup itself was 6 ms of host time per step)
         key = (tile_cfg, B, Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up, Kp, mode, want_stats, group_imgs, out_map is not None,
-               mask_src is None, row_scale is None, res_relu, res_up, res_unpool)
+               mask_src is None, row_scale is None, res_relu, res_up, res_unpool, _opts_key(pending_opts()))
         kname = _NAME_CACHE.get(key)
         modes = (nat.fn("diagan_conv_gemm_get_wino")(), nat.fn("diagan_conv_gemm_get_wino4x")(), nat.fn("diagan_conv_gemm_get_x3")(),
                  nat.fn("diagan_conv_gemm_get_x3b")())
@@ -568,15 +591,23 @@ def conv_fwd(geom, x, wf, bias=None, residual=None, pro=None, out=None, tile_cfg
                  up_in=up_in, wsite=wsite, wversion=wversion, out_map=out_map)
 
 
-def out_map_ok(geom, B, Hi, Wi, pro=None):
-    """Will conv_fwd(geom, x[B,Hi,Wi,Ci], w, out=..., out_map=...) run?  True iff the automatic choice for this plain launch is
-    the split-operand kernel (tile_cfg 17), the only one that writes through an output map."""
+def out_map_ok(geom, B, Hi, Wi, pro=None, wino=True):
+    """Will conv_fwd(geom, x[B,Hi,Wi,Ci], w, out=..., out_map=..., wino=wino) run?  True iff the automatic choice for this plain launch,
+    under the options pending for it (next_opts) and with Winograd kept out where wino is False -- the launch's own inputs -- is the
+    split-operand kernel (tile_cfg 17), the only one that writes through an output map."""
     Ho, Wo = geom.out_hw(Hi, Wi)
     sy, dr, off, up = geom.fwd_params()
     ws = _splitk_ws(torch.device('cuda', torch.cuda.current_device()))
     mode = pro[0] if pro is not None else PRO_NONE
-    return nat.fn("diagan_conv_gemm_final_cfg")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up, geom.Kp, 1,
-                                               ws.numel(), 0, mode, 1, 0) == 17
+    pend = None if wino else pending_opts()
+    if pend is not None:
+        nat.call("diagan_conv_gemm_next_opts", _ct.byref(_without_wino(pend)))
+    try:
+        return nat.fn("diagan_conv_gemm_final_cfg")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up, geom.Kp, 1,
+                                                   ws.numel(), 0, mode, 1, 0) == 17
+    finally:
+        if pend is not None:
+            nat.call("diagan_conv_gemm_next_opts", _ct.byref(pend))
 
 
 def conv_dgrad(geom, dy, wd, in_hw, residual=None, mask_src=None, mask_slope=0.0, out=None, tile_cfg=0,

@@ -34,7 +34,7 @@ FUSED_PREP = os.environ.get("DIAGAN_SG2_FUSED_PREP", "1") == "1"
 # iteration: 82 -> 99 images/s).  Measured against the oracle in float64 the two convolution paths are equally far from
 # the truth: the three-iteration trajectory at 8 x 8 and 16 x 16 (tools/sg2_trajectory.py) and the ill-conditioned
 # NoiseInjection strength gradients at 256 x 256 (tools/sg2_noise_grad.py); profiles/r02_sg2_winograd.md.
-# DIAGAN_SG2_WINO=0 keeps these ops on the implicit GEMM.
+# DIAGAN_SG2_WINO=0 keeps these ops on the implicit GEMM (its automatic choice, the split-operand kernels and output maps included).
 SG2_WINO = os.environ.get("DIAGAN_SG2_WINO", "1") == "1"
 # the parity classes of the stride-2 transposed gathers write straight into the interleaved result where the launch runs on the
 # split-operand kernel (csrc/conv_gemm_x3b.hip, ConvGemmArgs::map); DIAGAN_SG2_OUT_MAP=0: compute each class, then copy it into place
@@ -101,7 +101,7 @@ def _up2_gather(x, w, n_out, R, S, C, out_hw):
                 ws = w4[:, ry][:, :, sx].reshape(n_out, ny * nx * C)
                 if ws.shape[1] != sub.Kp:
                     ws = F.pad(ws, (0, sub.Kp - ws.shape[1]))
-            if OUT_MAP and K.out_map_ok(sub, B, H, W):
+            if OUT_MAP and K.out_map_ok(sub, B, H, W, wino=SG2_WINO):
                 # the class interleaves itself: the split-operand kernel writes pixel (my, mx) of the class to (2 (my - ty) + cy,
                 # 2 (mx - tx) + cx) and drops the surplus border of the symmetric padding (no copy pass; round 6)
                 K.conv_fwd(sub, x, ws.contiguous(), wino=SG2_WINO, out=out,

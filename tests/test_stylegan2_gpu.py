@@ -38,39 +38,21 @@ CASES = [  # kind, B, H, W, Ci, Co, k, stride, pad
 ]
 
 
-def _ref_op(kind, x, w, stride, pad):
-    if kind == "conv":
-        return F.conv2d(x, w, stride=stride, padding=pad)
-    return F.conv_transpose2d(x, w.transpose(0, 1), stride=stride, padding=pad)
-
-
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(map(str, c)))
 def test_diffconv_first_and_second_order(case):
     """y, dy/dx, dy/dw and the gradients OF a function of the input gradient (R1's structure) and of the weight
-    gradient, against torch autograd over F.conv2d / F.conv_transpose2d on the CPU in float64."""
+    gradient, against torch autograd over F.conv2d / F.conv_transpose2d on the CPU in float64 (tests/sg2_harness.py)."""
     from diagan.ops import diffconv as dc
+    from sg2_harness import OUTPUTS, first_and_second_order, ref_op
     kind, B, H, W, Ci, Co, k, stride, pad = case
     g = torch.Generator().manual_seed(hash(case) % 1000)
     x0 = torch.randn(B, Ci, H, W, generator=g, dtype=torch.float64)
     w0 = torch.randn(Co, Ci, k, k, generator=g, dtype=torch.float64) / (Ci * k * k) ** 0.5
-
-    def run(x, w, op, nhwc):
-        x = x.clone().requires_grad_(True)
-        w = w.clone().requires_grad_(True)
-        y = op(x.permute(0, 2, 3, 1).contiguous() if nhwc else x, w)
-        if nhwc:
-            y = y.permute(0, 3, 1, 2)
-        cot = torch.cos(torch.arange(y.numel(), dtype=torch.float64).view(y.shape)).to(y)
-        gx, gw = torch.autograd.grad((y * cot).sum() + 0.5 * (y ** 2).sum(), (x, w), create_graph=True)
-        penalty = (gx ** 2).sum() + (gw ** 2).sum()
-        ggx, ggw = torch.autograd.grad(penalty, (x, w))
-        return [t.detach().cpu().double() for t in (y, gx, gw, ggx, ggw)]
-
-    ours = run(x0.float().cuda(), w0.float().cuda(),
-               (lambda x, w: dc.conv2d(x, w, stride, pad)) if kind == "conv" else
-               (lambda x, w: dc.conv_transpose2d(x, w, stride, pad)), True)
-    ref = run(x0, w0, lambda x, w: _ref_op(kind, x, w, stride, pad), False)
-    for name, a, b in zip(("y", "dx", "dw", "d(penalty)/dx", "d(penalty)/dw"), ours, ref):
+    ours = first_and_second_order(x0.float().cuda(), w0.float().cuda(),
+                                  (lambda x, w: dc.conv2d(x, w, stride, pad)) if kind == "conv" else
+                                  (lambda x, w: dc.conv_transpose2d(x, w, stride, pad)), True)
+    ref = first_and_second_order(x0, w0, lambda x, w: ref_op(kind, x, w, stride, pad), False)
+    for name, a, b in zip(OUTPUTS, ours, ref):
         close(a, b, what=f"{case} {name}")
 
 
