@@ -766,6 +766,29 @@ int diagan_augment_forward(const float* img, const double* params, int B, int H,
 int diagan_augment_backward(const float* gout, const double* params, int B, int H, int W, int pad_x1, int pad_x2, int pad_y1,
                             int pad_y2, float* gimg, void* workspace, void* stream);
 
+/* ---- FID Inception-v3 feature extractor (pytorch-fid InceptionV3, use_fid_inception=True), DESIGN §8g -------------------------
+ * NHWC fp32 throughout; inference only.  Every output element comes from one thread or one workgroup in a fixed order that
+ * does not depend on the batch (no split-K, no atomics): bit-identical reruns, batch-invariant features.  The caller owns all memory.
+ * incep_conv_kp: the packed row length Kp of an R x S x Ci filter (R S Ci rounded up to the K-step).
+ * incep_conv: y[.., c0_out + co] = act(bias[co] + sum_{r,s,ci} w[co][(r S + s) Ci + ci] x[.., iy, ix, c0_in + ci]) with
+ *   iy = oy stride_h - pad_h + r, ix = ox stride_w - pad_w + s (zero outside the image); x is [B][H][W][ctot_in], y is
+ *   [B][Ho][Wo][ctot_out] and only channels [c0_out, c0_out + Co) are written; w is [Co][Kp] with zeros past R S Ci; act = ReLU
+ *   when relu.  Ci, ctot_in and c0_in multiples of 4; x and w 16-byte aligned.  fp32 products and sums on the fp32 matrix pipe.
+ * incep_pool3: 3 x 3 pool of channels [c0_in, c0_in + C) into [c0_out, c0_out + C): mode 0 max stride 2 pad 0, mode 1 max
+ *   stride 1 pad 1, mode 2 average stride 1 pad 1 dividing by the taps inside the image (count_include_pad=False).
+ * incep_gap: y[b][c] = mean over the HW pixels of x[b][.][c], summed in pixel order.
+ * incep_prep: x [B][3][H][W] (or [B][H][W][3] with nhwc) -> y [B][Ho][Wo][4] = a * bilinear(x) + b (align_corners=False, no
+ *   antialias; resize == 0 copies, Ho = H, Wo = W), channel 3 = 0. */
+int diagan_incep_conv_kp(int R, int S, int Ci);
+int diagan_incep_conv(const float* x, int B, int H, int W, int ctot_in, int c0_in, int Ci, const float* w, const float* bias, int Co,
+                      int R, int S, int Kp, int stride_h, int stride_w, int pad_h, int pad_w, float* y, int Ho, int Wo, int ctot_out,
+                      int c0_out, int relu, void* stream);
+int diagan_incep_pool3(const float* x, int B, int H, int W, int ctot_in, int c0_in, int C, float* y, int Ho, int Wo, int ctot_out,
+                       int c0_out, int mode, void* stream);
+int diagan_incep_gap(const float* x, int B, int HW, int C, float* y, void* stream);
+int diagan_incep_prep(const float* x, int nhwc, int B, int H, int W, float* y, int Ho, int Wo, int resize, float a, float b,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

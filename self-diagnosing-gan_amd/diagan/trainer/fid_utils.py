@@ -1,7 +1,8 @@
 """Frechet Inception Distance in feature space on the HIP engine (reference: diagan-pkg/diagan/trainer/fid_utils.py, adopted there
 from the official TTUR fid.py; the npz statistics contract of fid_score.py:17-75).  Same names, arguments and results where the
-reference has them; the Inception feature extractor itself is out of scope (its weights are not part of this repository):
-features come in as [N, D] arrays.
+reference has them.  Features come in as [N, D] arrays, or are computed from images by the FID Inception-v3 network on the device
+(diagan.models.inception.InceptionV3; its weights are not part of this repository): get_activations,
+calculate_image_statistics, fid_from_images and generator_statistics.
 
 All arithmetic is float64 on the device (csrc/fid_stats.hip):
   statistics   per-row finite mask, column means, and the centred co-moment Xc^T Xc on the fp64 MFMA GEMM, merged batch by batch
@@ -17,7 +18,8 @@ from diagan import _native as nat
 from diagan.ops import linalg64 as la
 
 __all__ = ['calculate_frechet_distance', 'calculate_activation_statistics', 'calculate_feature_statistics', 'FeatureStatistics',
-           'load_statistics', 'save_statistics', 'fid_from_features']
+           'load_statistics', 'save_statistics', 'fid_from_features', 'get_activations', 'calculate_image_statistics',
+           'fid_from_images', 'generator_statistics']
 
 _CHUNK = 8192      # rows of centred features per co-moment GEMM (workspace: _CHUNK x D doubles)
 
@@ -193,3 +195,90 @@ def fid_from_features(real, fake, device=None, verbose=True):
         stats.append(st.finalize())
     (mu1, s1), (mu2, s2) = stats
     return calculate_frechet_distance(mu1, s1, mu2, s2, device=device)
+
+
+# ---- from images: the FID Inception-v3 network on the device (diagan.models.inception) --------------------------
+def _image_batches(images, batch_size):
+    """Batches of an [N, 3, H, W] array / tensor, or the items of an iterable of such batches, as float32 tensors."""
+    if isinstance(images, (np.ndarray, torch.Tensor)):
+        x = torch.as_tensor(images)
+        if x.dim() != 4:
+            raise RuntimeError(f"images must be [N, 3, H, W], got {tuple(x.shape)}")
+        for lo in range(0, x.shape[0], batch_size):
+            yield x[lo:lo + batch_size]
+    else:
+        for b in images:
+            b = b[0] if isinstance(b, (tuple, list)) else b
+            yield torch.as_tensor(b)
+
+
+def _model_features(model, batch, dims, device):
+    with torch.no_grad():
+        return model.features(batch.to(device=device, dtype=torch.float32, non_blocking=True), dims=dims)
+
+
+def get_activations(images, model, batch_size=50, dims=2048, device=None, verbose=False):
+    """Features of `dims` width (pool-3 for 2048) of every image: [N, dims] float64 numpy array, the name and contract of
+    inclusive_gan.py's get_activations.  images: [N, 3, H, W] in (0, 1) (the model's resize_input / normalize_input apply);
+    model: diagan.models.inception.InceptionV3.  Unlike the reference, the last partial batch is kept, not dropped: all N
+    images are used."""
+    device = _dev(device, images)
+    x = torch.as_tensor(images)
+    out = np.empty((x.shape[0], dims))
+    lo = 0
+    for i, batch in enumerate(_image_batches(x, batch_size)):
+        if verbose:
+            print(f"\rPropagating batch {i + 1}/{-(-x.shape[0] // batch_size)}", end='', flush=True)
+        f = _model_features(model, batch, dims, device)
+        out[lo:lo + f.shape[0]] = f.cpu().numpy()
+        lo += f.shape[0]
+    if verbose:
+        print(" done")
+    return out
+
+
+def calculate_image_statistics(images_or_iterable, model, batch_size=50, dims=2048, device=None):
+    """(mu, sigma) float64 device tensors of the features of images: an [N, 3, H, W] array / tensor cut into batches of
+    batch_size, or an iterable of batches (e.g. a DataLoader; (images, labels) items use the images).  Batches stream into a
+    FeatureStatistics: the features of all images are never held at once."""
+    device = _dev(device, images_or_iterable if isinstance(images_or_iterable, torch.Tensor) else None)
+    st = FeatureStatistics(dims, device)
+    for batch in _image_batches(images_or_iterable, batch_size):
+        st.update(_model_features(model, batch, dims, device))
+    return st.finalize()
+
+
+def fid_from_images(real, fake, model, batch_size=50, dims=2048, device=None):
+    """FID between two image sets (arrays, tensors or iterables of batches, see calculate_image_statistics): images ->
+    features -> float64 statistics -> Frechet distance, all on the device."""
+    mu1, s1 = calculate_image_statistics(real, model, batch_size, dims, device)
+    mu2, s2 = calculate_image_statistics(fake, model, batch_size, dims, device)
+    return calculate_frechet_distance(mu1, s1, mu2, s2, device=mu1.device)
+
+
+def generator_statistics(netG, model, num_images, batch_size=50, dims=2048, device=None, seed=None):
+    """(mu, sigma) float64 device tensors of num_images samples of a generator, to compare with saved statistics
+    (load_statistics).  The generator's [-1, 1] images go into the network through the input prep's affine
+    (a = 1, b = 0 replaces normalize_input's 2x - 1), NHWC straight from generate_images_nhwc where the model has one."""
+    device = _dev(device)
+    st = FeatureStatistics(dims, device)
+    gen = torch.Generator(device=device)
+    if seed is not None:
+        gen.manual_seed(seed)
+    was_training = netG.training
+    netG.eval()
+    try:
+        with torch.no_grad():
+            for lo in range(0, num_images, batch_size):
+                n = min(batch_size, num_images - lo)
+                noise = torch.randn((n, netG.nz), device=device, generator=gen if seed is not None else None)
+                if hasattr(netG, 'generate_images_nhwc'):
+                    img, _ = netG.generate_images_nhwc(n, device=device, noise=noise)
+                    f = model.features(img.float()[..., :3], dims=dims, nhwc=True, scale=1.0, shift=0.0)
+                else:
+                    img = netG.generate_images(n, device=device, noise=noise)
+                    f = model.features(img.float(), dims=dims, scale=1.0, shift=0.0)
+                st.update(f)
+    finally:
+        netG.train(was_training)
+    return st.finalize()
