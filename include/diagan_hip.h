@@ -789,6 +789,25 @@ int diagan_incep_gap(const float* x, int B, int HW, int C, float* y, void* strea
 int diagan_incep_prep(const float* x, int nhwc, int B, int H, int W, float* y, int Ho, int Wo, int resize, float a, float b,
                       void* stream);
 
+/* ---- Kernel Inception Distance and Inception Score (torch-mimicry compute_kid / compute_is), DESIGN §8h ----------------------
+ * float64 throughout; every reduction in a fixed order (bit-identical reruns, no float atomics).  The caller owns all memory.
+ * poly_mmd_sums: for each of S subsets of m rows, with k(a, b) = (gamma <a, b> + coef0)^degree (degree >= 1, by repeated
+ *   multiplication): out[3 s + 0] = sum_{i != j} k(x_i, x_j), out[3 s + 1] = sum_{i != j} k(y_i, y_j), out[3 s + 2] =
+ *   sum_{i, j} k(x_i, y_j), where x_i = X[idx_x[s m + i]] and y_j = Y[idx_y[s m + j]] (a NULL table: rows 0..m-1).  X is
+ *   [Nx][ldx] and Y [Ny][ldy], each fp32 or (x_f64 / y_f64) fp64.  One launch covers all subsets and products; the dot products
+ *   run on the fp64 matrix cores and no m x m matrix is stored.  A table entry outside its matrix reads as a zero row.
+ *   ws: S * diagan_poly_mmd_ws(m) doubles.  The sums of a subset do not depend on the other subsets of the launch.
+ * is_scores: logits [N][ld] fp32, C classes; split k is rows [k N / splits, (k + 1) N / splits); out[k] =
+ *   exp(mean_i sum_c p_ic log p_ic - sum_c pbar_c log pbar_c), p = softmax(logits) with the row maximum taken out, pbar the
+ *   split's column means of p, 0 log 0 = 0.  ws: diagan_is_ws(N, C, splits) doubles.  1 <= splits <= N, and a split of at most
+ *   65535 * 256 rows.  Logits are finite or -inf (probability 0) with at least one finite value per row; NaN or +inf give NaN. */
+int diagan_poly_mmd_ws(int m);
+int diagan_poly_mmd_sums(const void* X, int x_f64, int Nx, int ldx, const void* Y, int y_f64, int Ny, int ldy, const int* idx_x,
+                         const int* idx_y, int S, int m, int D, int degree, double gamma, double coef0, double* ws, double* out,
+                         void* stream);
+int diagan_is_ws(int N, int C, int splits);
+int diagan_is_scores(const float* logits, int N, int C, int ld, int splits, double* ws, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,10 +16,12 @@ import torch.nn as nn
 
 from diagan.ops import inception as K
 
-__all__ = ['InceptionV3', 'LAYERS', 'BN_EPS', 'FID_WEIGHTS_FILE', 'load_fid_state_dict', 'pack_layer', 'layer_flops']
+__all__ = ['InceptionV3', 'LAYERS', 'BN_EPS', 'FID_WEIGHTS_FILE', 'NUM_CLASSES', 'load_fid_state_dict', 'load_fid_classifier',
+           'pack_layer', 'pack_classifier', 'layer_flops']
 
 FID_WEIGHTS_FILE = 'pt_inception-2015-12-05-6726825d.pth'
 BN_EPS = 1e-3
+NUM_CLASSES = 1008       # the classes of the 2015 TF graph's fc head (the Inception Score reads its logits)
 
 
 def _basic(name, ci, co, k, stride=1, pad=0):
@@ -87,9 +89,8 @@ def _ignored(key):
     return key.startswith('fc.') or key.startswith('AuxLogits.') or key.endswith('num_batches_tracked')
 
 
-def load_fid_state_dict(weights=None):
-    """The torchvision-layout state dict of the FID network from a path, a state dict in either key layout, or (weights None)
-    the file named by DIAGAN_FID_WEIGHTS.  Checks every key and shape; a missing, unknown or mis-shaped tensor raises naming it."""
+def _resolve_weights(weights):
+    """A state dict from a path, a state dict, or (None) the file named by DIAGAN_FID_WEIGHTS."""
     if weights is None:
         weights = os.environ.get('DIAGAN_FID_WEIGHTS')
         if not weights:
@@ -101,6 +102,40 @@ def load_fid_state_dict(weights=None):
         weights = torch.load(weights, map_location='cpu', weights_only=True)
     if not isinstance(weights, dict):
         raise RuntimeError(f"InceptionV3 weights: expected a path or a state dict, got {type(weights).__name__}")
+    return weights
+
+
+def load_fid_classifier(weights=None):
+    """(fc.weight [1008, 2048], fc.bias [1008]) of the network's classifier head as float32 CPU tensors, from the same sources
+    as load_fid_state_dict (both key layouts name the head 'fc.*'); None when the weights carry no head.  A head with only one
+    of the two tensors, or a mis-shaped one, raises naming the key."""
+    weights = _resolve_weights(weights)
+    want = {'fc.weight': (NUM_CLASSES, 2048), 'fc.bias': (NUM_CLASSES,)}
+    if not any(k in weights for k in want):
+        return None
+    out = []
+    for key, shape in want.items():
+        if key not in weights:
+            raise RuntimeError(f"InceptionV3 weights: missing key '{key}'")
+        t = torch.as_tensor(weights[key]).detach()
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"InceptionV3 weights: '{key}' has shape {tuple(t.shape)}, expected {shape}")
+        out.append(t.to('cpu', torch.float32))
+    return tuple(out)
+
+
+def pack_classifier(weight, bias):
+    """The head as a 1 x 1 convolution for csrc/inception.hip: fp32 [1008][Kp] rows (zeros past 2048) and the bias."""
+    kp = K.conv_kp(1, 1, weight.shape[1])
+    w = torch.zeros((weight.shape[0], kp), dtype=torch.float32)
+    w[:, :weight.shape[1]] = weight
+    return w, bias.to(torch.float32).clone()
+
+
+def load_fid_state_dict(weights=None):
+    """The torchvision-layout state dict of the FID network from a path, a state dict in either key layout, or (weights None)
+    the file named by DIAGAN_FID_WEIGHTS.  Checks every key and shape; a missing, unknown or mis-shaped tensor raises naming it."""
+    weights = _resolve_weights(weights)
     sd = {}
     for key, val in weights.items():
         if _ignored(key):
@@ -213,6 +248,7 @@ class InceptionV3(nn.Module):
         if not self.output_blocks or min(self.output_blocks) < 0 or max(self.output_blocks) > 3:
             raise ValueError('Last possible output block index is 3')
         self.last_needed_block = max(self.output_blocks)
+        weights = _resolve_weights(weights)
         sd = load_fid_state_dict(weights)
         self._names = []
         for layer in LAYERS:
@@ -221,6 +257,17 @@ class InceptionV3(nn.Module):
             self.register_buffer(key + '__w', w, persistent=False)
             self.register_buffer(key + '__b', b, persistent=False)
             self._names.append(layer)
+        head = load_fid_classifier(weights)
+        self.has_classifier = head is not None
+        # The packed head is NOT a registered buffer: tests/test_inception_host.py pins named_buffers() at the 2 x 94 convolution
+        # tensors, for weights that carry fc.* too.  _apply() below moves it with the module (.to(), .cuda(), .cpu()).
+        self._fc = pack_classifier(*head) if head is not None else None
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        if self._fc is not None:
+            self._fc = tuple(fn(t) for t in self._fc)
+        return self
 
     # ---- layers ------------------------------------------------------------------------------------------------------------
     def _wb(self, layer):
@@ -346,6 +393,16 @@ class InceptionV3(nn.Module):
         blk = self.BLOCK_INDEX_BY_DIM[dims]
         y = self.run_nhwc(inp, nhwc=nhwc, scale=scale, shift=shift, last_block=blk)[blk]
         return y.reshape(y.shape[0], dims) if y.shape[1] * y.shape[2] == 1 else K.global_avg(y)
+
+    def logits(self, inp, nhwc=False, scale=None, shift=None):
+        """[B, 1008] float32 device logits of the classifier head, fc.weight pool3 + fc.bias, as a 1 x 1 convolution over the
+        [B, 1, 1, 2048] pool-3 features (the Inception Score's input).  Needs weights that carry 'fc.*'."""
+        if not self.has_classifier:
+            raise RuntimeError("InceptionV3.logits: the weights this model was built from carry no classifier head "
+                               "('fc.weight' [1008, 2048], 'fc.bias' [1008])")
+        pool3 = self.run_nhwc(inp, nhwc=nhwc, scale=scale, shift=shift, last_block=3)[3]      # moves the module to inp's device
+        w, b = self._fc
+        return K.conv(pool3, w, b, 1, 1, relu=False).reshape(pool3.shape[0], NUM_CLASSES)
 
     @torch.no_grad()
     def forward(self, inp):
