@@ -4,7 +4,9 @@
  * step and LDR scorer are Python calling ATen/cuDNN ops and NumPy.  The only native boundary in
  * the reference is the StyleGAN2 pybind pair (diagan-pkg/diagan/models/op/fused_bias_act.cpp:4-20,
  * upfirdn2d.cpp:4-22), whose conventions this ABI keeps: launch on the caller's stream, no hidden
- * synchronisation, no global mutable state, errors surfaced to Python as RuntimeError.
+ * synchronisation, errors surfaced to Python as RuntimeError.  State: kernel selection travels with
+ * the call (diagan_conv_opts); the process-wide setters below are mutable globals for diagnostics
+ * only, and the DIAGAN_* environment switches are read once.
  * Every entry point below names the reference Python op (file:line) it replaces.
  *
  * Conventions
@@ -14,7 +16,7 @@
  *   - `stream` is a hipStream_t (0 = default stream); nothing synchronises;
  *   - activations are NHWC fp32 ("pixels x channels" row-major), channel counts padded to a
  *     multiple of 4; weights are consumed in the packed GEMM layouts produced by
- *     diagan_weight_prep (see DESIGN.md "Data layout in HBM").
+ *     diagan_pack_weights / diagan_pack_oihw / diagan_pack_batched (see DESIGN.md "Data layout in HBM").
  */
 #ifndef DIAGAN_HIP_H
 #define DIAGAN_HIP_H

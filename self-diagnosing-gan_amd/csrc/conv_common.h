@@ -10,6 +10,7 @@
 //     transposed conv / dgrad (stride s, p)  : sy = 1, dr = -1, off = +p, up = s
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 namespace diagan {
 
@@ -27,6 +28,25 @@ enum ProMode : int {
   PRO_BOX = 5,
   PRO_BOX_RELU = 6,
 };
+
+// The run-time prologue mode as the compile-time PRO of a kernel family: `launch` is a generic lambda that takes the mode as a type,
+//   with_pro(a.pro_mode, [&](auto pro) { return launch_x<decltype(pro)::value>(a, st); })
+// and is instantiated for the five convolution prologues (with_pro_relu: the two of the pooled modes, none / ReLU).
+template <int P> using ProTag = std::integral_constant<int, P>;
+template <class F>
+static inline int with_pro(int pro_mode, F&& launch) {
+  switch (pro_mode) {
+    case PRO_NONE: return launch(ProTag<PRO_NONE>{});
+    case PRO_RELU: return launch(ProTag<PRO_RELU>{});
+    case PRO_AFFINE_RELU: return launch(ProTag<PRO_AFFINE_RELU>{});
+    case PRO_LRELU: return launch(ProTag<PRO_LRELU>{});
+    default: return launch(ProTag<PRO_AFFINE>{});
+  }
+}
+template <class F>
+static inline int with_pro_relu(int pro_mode, F&& launch) {
+  return pro_mode == PRO_RELU ? launch(ProTag<PRO_RELU>{}) : launch(ProTag<PRO_NONE>{});
+}
 
 struct ConvGeom {
   int B, Hi, Wi, Ci;   // gathered tensor (conv input for fwd / wgrad, dy for dgrad)

@@ -19,6 +19,7 @@
 //
 // Roofline: MFMA fp32 (algorithmic FLOP = 2*M*Co*K).
 #include "conv_common.h"
+#include "switches.h"
 #include <type_traits>
 #include <stdlib.h>
 #include <string.h>
@@ -701,10 +702,7 @@ static int g_gemm_x3 = -1;                        // -1: DIAGAN_GEMM_X3 / defaul
 // default; 0 / 1: diagan_conv_gemm_set_x3b.  The automatic choice upgrades an implicit-GEMM pick (never a Winograd one) where the
 // launch has at least `x3b_min_tiles()` 128 x 128 tiles and four K-steps.
 static int g_gemm_x3b = -1;
-static int x3b_min_tiles() {
-  static const int env = getenv("DIAGAN_GEMM_X3B_MIN_TILES") ? atoi(getenv("DIAGAN_GEMM_X3B_MIN_TILES")) : 192;
-  return env;
-}
+static int x3b_min_tiles() { return kGemmX3bMinTiles.env(); }
 // the output map of the NEXT diagan_conv_gemm call of this thread (diagan_conv_gemm_out_map); like the weights hint it holds for
 // exactly one call
 static thread_local OutMap g_map_next = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -723,20 +721,11 @@ static const CallOpts kNoOpts = {-1, -1, -1, -1, -1, -1, 0, -1, nullptr, 0};
 static thread_local CallOpts g_opts_next = kNoOpts, g_opts_now = kNoOpts;
 static thread_local int g_last_cfg = 0;           // tile configuration the last call of this thread resolved to
 int call_opt_wino4x() { return g_opts_now.wino4x; }          // (conv_wino4.hip: wino4_get_x3)
-static int sel_wino() {
-  static const int env = getenv("DIAGAN_WINO") ? atoi(getenv("DIAGAN_WINO")) : 1;
-  return g_opts_now.wino >= 0 ? g_opts_now.wino : (g_wino >= 0 ? g_wino : env);
-}
+static int sel_wino() { return kWino.get(g_opts_now.wino, g_wino); }
 static int sel_wino4() { return g_opts_now.wino4 >= 0 ? g_opts_now.wino4 : g_wino4; }      // (-1: the environment's DIAGAN_WINO4 decides, at its use)
 static int sel_force_ksplit() { return g_opts_now.force_ksplit > 0 ? g_opts_now.force_ksplit : g_force_ksplit; }
-static bool gemm_x3_on() {
-  static const int env = getenv("DIAGAN_GEMM_X3") ? atoi(getenv("DIAGAN_GEMM_X3")) : 1;      // on: SNGAN-32 5270-5281 -> 5355 images/s
-  return (g_opts_now.gemm_x3 >= 0 ? g_opts_now.gemm_x3 : (g_gemm_x3 >= 0 ? g_gemm_x3 : env)) != 0;
-}
-static bool gemm_x3b_on() {
-  static const int env = getenv("DIAGAN_GEMM_X3B") ? atoi(getenv("DIAGAN_GEMM_X3B")) : 1;
-  return (g_opts_now.gemm_x3b >= 0 ? g_opts_now.gemm_x3b : (g_gemm_x3b >= 0 ? g_gemm_x3b : env)) != 0;
-}
+static bool gemm_x3_on() { return kGemmX3.get(g_opts_now.gemm_x3, g_gemm_x3) != 0; }
+static bool gemm_x3b_on() { return kGemmX3b.get(g_opts_now.gemm_x3b, g_gemm_x3b) != 0; }
 static bool x3b_takes(const ConvGemmArgs& a, int cfg, int64_t ws_floats) {
   if (!gemm_x3b_on() || !(cfg == 1 || cfg == 3 || cfg == 5 || cfg == 7 || cfg == 8)) return false;
   const ConvGeom& g = a.g;
@@ -755,10 +744,17 @@ static int g_splitk_fused = -1;                   // -1: DIAGAN_SPLITK_FUSED / d
 static int* g_tickets = nullptr;                  // diagnostics: diagan_conv_gemm_set_splitk_tickets
 static long g_ticket_slots = 0;
 static int* splitk_tickets(long tiles) {
-  static const int env = getenv("DIAGAN_SPLITK_FUSED") ? atoi(getenv("DIAGAN_SPLITK_FUSED")) : 0;
-  if (!(g_opts_now.splitk_fused >= 0 ? g_opts_now.splitk_fused : (g_splitk_fused >= 0 ? g_splitk_fused : env))) return nullptr;
+  if (!kSplitkFused.get(g_opts_now.splitk_fused, g_splitk_fused)) return nullptr;
   if (g_opts_now.tickets) return tiles <= g_opts_now.ticket_slots ? g_opts_now.tickets : nullptr;
   return (g_tickets && tiles <= g_ticket_slots) ? g_tickets : nullptr;        // (no buffer: the second launch, as with the switch off)
+}
+
+// the split-K second stage over a.M pixels (splitk_epilogue_kernel); `what` names the launch in the error text
+static int splitk_second_stage(const ConvGemmArgs& a, hipStream_t st, const char* what) {
+  long blocks = ((long)a.M * (a.g.Co / 4) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((int)blocks), dim3(256), 0, st, a);
+  return check_launch(what);
 }
 
 template <int BM, int BN, int WM, int WN, int BK, int PRO, bool STAMP = false, bool FP = false, int KG = 1>
@@ -771,12 +767,7 @@ static int launch_one(const ConvGemmArgs& a, hipStream_t st) {
   static FuncAttrLatch latch;
   DG_LDS(latch, kern, lds);
   hipLaunchKernelGGL(kern, dim3(tiles, a.ksplit), dim3(256 * KG), lds, st, a);
-  if (a.ksplit > 1) {
-    long blocks = ((long)a.M * (a.g.Co / 4) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((int)blocks), dim3(256), 0, st, a);
-  }
-  return check_launch("conv_gemm");
+  return a.ksplit > 1 ? splitk_second_stage(a, st, "conv_gemm") : check_launch("conv_gemm");
 }
 
 // SPEC: one kernel per prologue mode (the production tiles); otherwise the mode is a run-time argument.
@@ -788,15 +779,8 @@ static int launch_cfg(const ConvGemmArgs& a, hipStream_t st) {
     if (a.pro_mode == PRO_RELU) return launch_one<BM, BN, WM, WN, BK, PRO_RELU, true, FP>(a, st);
     return set_err(DIAGAN_EUNSUP, "conv_gemm: the stamped diagnostic kernels exist for prologue modes 0 and 1");
   }
-  if (SPEC) {
-    switch (a.pro_mode) {
-      case PRO_NONE: return launch_one<BM, BN, WM, WN, BK, SPEC ? PRO_NONE : -1, false, FP, KG>(a, st);
-      case PRO_RELU: return launch_one<BM, BN, WM, WN, BK, SPEC ? PRO_RELU : -1, false, FP, KG>(a, st);
-      case PRO_AFFINE_RELU: return launch_one<BM, BN, WM, WN, BK, SPEC ? PRO_AFFINE_RELU : -1, false, FP, KG>(a, st);
-      case PRO_LRELU: return launch_one<BM, BN, WM, WN, BK, SPEC ? PRO_LRELU : -1, false, FP, KG>(a, st);
-      default: return launch_one<BM, BN, WM, WN, BK, SPEC ? PRO_AFFINE : -1, false, FP, KG>(a, st);
-    }
-  }
+  if (SPEC)
+    return with_pro(a.pro_mode, [&](auto pro) { return launch_one<BM, BN, WM, WN, BK, SPEC ? decltype(pro)::value : -1, false, FP, KG>(a, st); });
   return launch_one<BM, BN, WM, WN, BK, -1, false, FP, KG>(a, st);
 }
 
@@ -804,10 +788,7 @@ static int launch_cfg(const ConvGemmArgs& a, hipStream_t st) {
 
 using namespace diagan;
 
-static bool split128_enabled() {
-  static const bool on = getenv("DIAGAN_SPLIT128") && atoi(getenv("DIAGAN_SPLIT128")) > 0;
-  return on;
-}
+static bool split128_enabled() { return kSplit128.env() > 0; }
 
 // Tile selection used when tile_cfg == 0.  Measured on MI355X (tools/tile_sweep.py, profiles/r02_tile_sweep.md):
 //  * 64-column outputs (the 64x64-resolution blocks of SNGAN-64): a 256x64 tile whose waves own 64x64 sub-tiles needs
@@ -840,8 +821,7 @@ DIAGAN_API int diagan_conv_gemm_pick_cfg(int M, int Co, int Kp, int allow_split)
   if (bias * q128 * waste128 > q64 * waste64) return 1;
   // at most one 64x64 tile per CU and a K loop that is worth halving but too short for split-K launches: two K-groups in
   // one workgroup (tile_cfg 14) put two waves on every SIMD.  DIAGAN_KG2=0: off.
-  static const int kg2 = getenv("DIAGAN_KG2") ? atoi(getenv("DIAGAN_KG2")) : 1;
-  if (kg2 && t64 <= 256 && Kp >= 16 * 32 && diagan_conv_gemm_pick_ksplit(M, Co, Kp, small) == 1) return 14;
+  if (kKg2.env() && t64 <= 256 && Kp >= 16 * 32 && diagan_conv_gemm_pick_ksplit(M, Co, Kp, small) == 1) return 14;
   return small;
 }
 
@@ -854,8 +834,7 @@ DIAGAN_API int diagan_conv_gemm_pick_cfg(int M, int Co, int Kp, int allow_split)
 //    GEMM itself 5-8 % faster -- 91 -> 85 us -- but the second-stage launches and slab traffic cost more than that
 //    over a whole training step: 2350 -> 2323 images/s.)
 DIAGAN_API int diagan_conv_gemm_pick_ksplit(int M, int Co, int Kp, int cfg) {
-  static const int env_forced = getenv("DIAGAN_KSPLIT") ? atoi(getenv("DIAGAN_KSPLIT")) : 0;   // tuning experiments only
-  const int forced = sel_force_ksplit() > 0 ? sel_force_ksplit() : env_forced;
+  const int forced = sel_force_ksplit() > 0 ? sel_force_ksplit() : kKsplit.env();
   if (forced > 0 && !(Co & 3)) return forced < Kp / 64 ? forced : (Kp / 64 > 0 ? Kp / 64 : 1);
   if (Co & 3) return 1;
   const int nk = Kp / 32;
@@ -982,7 +961,7 @@ DIAGAN_API int diagan_conv_gemm(const float* x, const float* w, float* y, const 
   a.slab = splitk_ws;
   a.tickets = nullptr;
   a.ksplit = 1;
-  a.tune = g_opts_now.tune >= 0 ? g_opts_now.tune : (g_tune_flags >= 0 ? g_tune_flags : kDefaultTune);
+  a.tune = first_set(g_opts_now.tune, g_tune_flags, kDefaultTune);
   a.stamps = nullptr;
   if (g_stamps) {
     const long wgs = (long)cdiv(a.M, bm) * cdiv(Co, diagan_conv_gemm_tile_cols(cfg)) * 16;   // room for up to 16 K splits
@@ -1015,10 +994,7 @@ DIAGAN_API int diagan_conv_gemm(const float* x, const float* w, float* y, const 
       e.M = B * (Ho >> 1) * (Wo >> 1);
       e.scale_split = a.scale_split >> 2;
       e.out_scale = a.out_scale;
-      long blocks = ((long)e.M * (Co / 4) + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((int)blocks), dim3(256), 0, st, e);
-      rc = check_launch("conv_wino_pool split-K epilogue");
+      rc = splitk_second_stage(e, st, "conv_wino_pool split-K epilogue");
     }
     return rc;
   }
@@ -1040,12 +1016,7 @@ DIAGAN_API int diagan_conv_gemm(const float* x, const float* w, float* y, const 
     a.ksplit = ks;
     a.slab = splitk_ws + wfl;
     int rc = launch_wino_unpool(a, splitk_ws, st);
-    if (rc == DIAGAN_OK && ks > 1) {
-      long blocks = ((long)a.M * (Co / 4) + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((int)blocks), dim3(256), 0, st, a);
-      rc = check_launch("conv_wino_unpool split-K epilogue");
-    }
+    if (rc == DIAGAN_OK && ks > 1) rc = splitk_second_stage(a, st, "conv_wino_unpool split-K epilogue");
     return rc;
   }
   if (cfg == 15) {
@@ -1075,12 +1046,7 @@ DIAGAN_API int diagan_conv_gemm(const float* x, const float* w, float* y, const 
     a.ksplit = ks;
     a.slab = splitk_ws + wfl;
     int rc = launch_wino4(a, splitk_ws, st);
-    if (rc == DIAGAN_OK && ks > 1) {
-      long blocks = ((long)a.M * (Co / 4) + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((int)blocks), dim3(256), 0, st, a);
-      rc = check_launch("conv_wino4 split-K epilogue");
-    }
+    if (rc == DIAGAN_OK && ks > 1) rc = splitk_second_stage(a, st, "conv_wino4 split-K epilogue");
     return rc;
   }
   if (cfg == 9) {
@@ -1102,12 +1068,7 @@ DIAGAN_API int diagan_conv_gemm(const float* x, const float* w, float* y, const 
     a.slab = splitk_ws + wfl;
     if (ks > 1) a.tickets = splitk_tickets((long)cdiv(a.M / 4, 64) * cdiv(Co, 64));
     int rc = launch_wino(a, splitk_ws, st);
-    if (rc == DIAGAN_OK && ks > 1 && !a.tickets) {
-      long blocks = ((long)a.M * (Co / 4) + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((int)blocks), dim3(256), 0, st, a);
-      rc = check_launch("conv_wino split-K epilogue");
-    }
+    if (rc == DIAGAN_OK && ks > 1 && !a.tickets) rc = splitk_second_stage(a, st, "conv_wino split-K epilogue");
     return rc;
   }
   DG_REQUIRE(!a.res_up, "conv_gemm: a half-resolution residual is added by the Winograd kernel only (tile_cfg 9; ask "
@@ -1165,9 +1126,8 @@ DIAGAN_API int diagan_conv_wino_supported(int Hi, int Wi, int Ci, int Ho, int Wo
 // DIAGAN_WINO=0 / DIAGAN_WINO_POOL=0 switch it off.
 DIAGAN_API int diagan_conv_wino_pool_supported(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy,
                                                int dr, int off, int up, int pro_mode, int64_t ws_floats) {
-  static const int pool_env = getenv("DIAGAN_WINO_POOL") ? atoi(getenv("DIAGAN_WINO_POOL")) : 1;
   const int wino = sel_wino();
-  if (!wino || !pool_env || dr != 1 || Co % 64 != 0 || Ci < 16 || !(pro_mode == PRO_NONE || pro_mode == PRO_RELU)) return 0;
+  if (!wino || !kWinoPool.env() || dr != 1 || Co % 64 != 0 || Ci < 16 || !(pro_mode == PRO_NONE || pro_mode == PRO_RELU)) return 0;
   if (!diagan_conv_wino_supported(Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up)) return 0;
   const long wfl = wino_ws_floats(Co, Ci);
   if (ws_floats < wfl) return 0;
@@ -1177,9 +1137,8 @@ DIAGAN_API int diagan_conv_wino_pool_supported(int B, int Hi, int Wi, int Ci, in
 // tile_cfg 12: the data-gradient of such a layer from the HALF-resolution gradient (same nine products, see conv_wino_pool.hip)
 DIAGAN_API int diagan_conv_wino_unpool_supported(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy,
                                                  int dr, int off, int up, int64_t ws_floats) {
-  static const int pool_env = getenv("DIAGAN_WINO_POOL") ? atoi(getenv("DIAGAN_WINO_POOL")) : 1;
   const int wino = sel_wino();
-  if (!wino || !pool_env || dr != -1 || Co % 64 != 0 || Ci < 16) return 0;
+  if (!wino || !kWinoPool.env() || dr != -1 || Co % 64 != 0 || Ci < 16) return 0;
   if (!diagan_conv_wino_supported(Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up)) return 0;
   const long wfl = wino_ws_floats(Co, Ci);
   if (ws_floats < wfl) return 0;
@@ -1198,20 +1157,15 @@ DIAGAN_API int diagan_conv_gemm_pick_cfg_geom(int B, int Hi, int Wi, int Ci, int
 static int pick_cfg_geom_impl(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr, int off,
                               int up, int Kp, int allow_split, int64_t ws_floats, bool allow_w4) {
   const int wino = sel_wino();
-  // one 512-thread workgroup per CU: below ~3/4 of the chip the implicit GEMM's smaller tiles win (8x8 / 4x4 blocks at
-  // batch 64: 128 workgroups, 325 vs 317 us; their data-gradients 330 vs 168 us)
-  static const int min_wgs = getenv("DIAGAN_WINO_MIN_WGS") ? atoi(getenv("DIAGAN_WINO_MIN_WGS")) : 192;
   if (wino && diagan_conv_wino_supported(Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up) &&
       ws_floats >= wino_ws_floats(Co, Ci) && Ci >= 16) {
-    static const int wsplit = getenv("DIAGAN_WINO_SPLIT") ? atoi(getenv("DIAGAN_WINO_SPLIT")) : 1;
+    const int wsplit = kWinoSplit.env();
     // F(4x4,3x3) (conv_wino4.hip, 32 tiles of 4x4 outputs x 64 channels per workgroup, ONE resident workgroup per CU): where its
     // launch-size policy (wino4_ksplit) expects it ahead of the F(2x2) kernel
-    static const int w4_env = getenv("DIAGAN_WINO4") ? atoi(getenv("DIAGAN_WINO4")) : 1;
-    static const int w4_min_ci = getenv("DIAGAN_WINO4_MIN_CI") ? atoi(getenv("DIAGAN_WINO4_MIN_CI")) : 64;
-    if (allow_w4 && w4_env && sel_wino4() != 0 && wino4_geom_ok(Ho, Wo, Ci) && Ci >= w4_min_ci && ws_floats >= wino4_ws_floats(Co, Ci) &&
+    if (allow_w4 && kWino4.env() && sel_wino4() != 0 && wino4_geom_ok(Ho, Wo, Ci) && Ci >= kWino4MinCi.env() && ws_floats >= wino4_ws_floats(Co, Ci) &&
         wino4_ksplit(B, Ho, Wo, Ci, Co, wsplit ? allow_split : 0, (long)ws_floats) > 0)
       return 13;
-    if (wino_ksplit(B, Ho, Wo, Ci, Co, wsplit ? allow_split : 0, (long)ws_floats, min_wgs) > 0) return 9;
+    if (wino_ksplit(B, Ho, Wo, Ci, Co, wsplit ? allow_split : 0, (long)ws_floats, kWinoMinWgs.env()) > 0) return 9;
   }
   return diagan_conv_gemm_pick_cfg(B * Ho * Wo, Co, Kp, allow_split);
 }

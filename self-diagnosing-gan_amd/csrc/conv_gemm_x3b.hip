@@ -25,6 +25,7 @@
 // the four dense sub-convolutions of a stride-2 transposed gather then interleave themselves and no copy pass follows.
 // Roofline: bf16 MFMA (dense 2.5 PFLOP/s / 6 products = 416.7 TFLOP/s fp32-equivalent); HBM traffic = operands once.
 #include "conv_common.h"
+#include "switches.h"
 #include "wino_weights.h"
 #include <stdlib.h>
 
@@ -664,21 +665,15 @@ bool gemm_x3b_geom_ok(const ConvGemmArgs& a) {
 // form 1 everywhere +0.8 % and +1.6 % on two boxes, -1.8 % and -1.3 ... -2.4 % on two others (profiles/r06_raw/sg2_ab*.txt) -- inside the
 // spread of this pool.
 // pieces per operand of the LARGE split-operand kernels (this file's first form, conv_wgrad_x3.hip): 3 = fp32-grade (default), 2 = opt-in
-static int g_x3_pieces = 0;                        // 0: the environment's DIAGAN_X3_PIECES (default 3)
-void x3_set_pieces(int n) { g_x3_pieces = (n == 2 || n == 3) ? n : 0; }
-int x3_pieces() {
-  static const int env = getenv("DIAGAN_X3_PIECES") ? atoi(getenv("DIAGAN_X3_PIECES")) : 3;
-  const int n = g_x3_pieces ? g_x3_pieces : env;
-  return n == 2 ? 2 : 3;
-}
-static int g_x3b_form = 0;                          // diagnostics / tests: 1 / 2 force a form (diagan_conv_gemm_x3b_force_form), 0: automatic
-void gemm_x3b_force_form(int form) { g_x3b_form = form; }
+static int g_x3_pieces = -1;                       // -1: the environment's DIAGAN_X3_PIECES (default 3)
+void x3_set_pieces(int n) { g_x3_pieces = (n == 2 || n == 3) ? n : -1; }
+int x3_pieces() { return kX3Pieces.get(-1, g_x3_pieces) == 2 ? 2 : 3; }
+static int g_x3b_form = -1;                         // diagnostics / tests: 1 / 2 force a form (diagan_conv_gemm_x3b_force_form), -1: DIAGAN_GEMM_X3B_FORM
+void gemm_x3b_force_form(int form) { g_x3b_form = form > 0 ? form : -1; }
 static int x3b_form(long tiles2, int nk) {
-  static const int env0 = getenv("DIAGAN_GEMM_X3B_FORM") ? atoi(getenv("DIAGAN_GEMM_X3B_FORM")) : 0;
-  const int env = g_x3b_form ? g_x3b_form : env0;
-  static const int min_tiles2 = getenv("DIAGAN_GEMM_X3B_FORM2_TILES") ? atoi(getenv("DIAGAN_GEMM_X3B_FORM2_TILES")) : 512;
+  const int forced = kGemmX3bForm.get(-1, g_x3b_form), min_tiles2 = kGemmX3bForm2Tiles.env();
   if (x3_pieces() == 2) return 1;                    // (the two-piece mode exists in the first form only)
-  if (env == 1 || env == 2) return env;
+  if (forced == 1 || forced == 2) return forced;
   // (K loops of fewer than 8 steps: 1x1 / stride 2 from 128 channels, 316 us against 288 -- the epilogue is a quarter of such a tile)
   return tiles2 >= min_tiles2 && nk >= 8 ? 2 : 1;
 }

@@ -18,6 +18,7 @@
 // Same gather formula / prologue / epilogue semantics as conv_gemm_kernel.  Roofline: LDS bandwidth for the
 // forward (one 16-byte A read per lane per 4 instructions), HBM / L2 for the weight gradient.
 #include "conv_common.h"
+#include "switches.h"
 #include <stdlib.h>
 
 namespace diagan {
@@ -452,8 +453,7 @@ DIAGAN_API int diagan_conv3x3_co4(const float* x, const float* w, float* y, cons
 
 // 1 if diagan_conv3x3_ci4 takes this layer: forward 3x3 / stride 1 / pad 1 from 4 input channels, Co a multiple of 32
 DIAGAN_API int diagan_conv3x3_ci4_supported(int Ci, int Co, int R, int S, int sy, int dr, int off, int up) {
-  static const int env = getenv("DIAGAN_CONV_CI4") ? atoi(getenv("DIAGAN_CONV_CI4")) : 1;
-  return env && R == 3 && S == 3 && sy == 1 && up == 1 && dr == 1 && off == -1 && Ci == 4 && Co >= 32 && Co <= 256 && (Co % 32) == 0;
+  return kConvCi4.env() && R == 3 && S == 3 && sy == 1 && up == 1 && dr == 1 && off == -1 && Ci == 4 && Co >= 32 && Co <= 256 && (Co % 32) == 0;
 }
 
 // y = conv3x3(x) * scale + bias for such a layer (no prologue, residual, mask or statistics: the discriminators' first

@@ -14,6 +14,7 @@
 //
 // Roofline: MFMA fp32 (algorithmic FLOP = 2*M*Co*K).
 #include "conv_common.h"
+#include "switches.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -815,11 +816,7 @@ DIAGAN_API int diagan_conv_wgrad_batch_max(void) { return WG_BATCH_MAX; }
 // DIAGAN_WINO=0 / diagan_conv_gemm_set_wino(0) is set.
 DIAGAN_API int diagan_conv_wgrad_uses_wino(int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr,
                                            int off, int up, int Kp) {
-  static const int wino_env = getenv("DIAGAN_WINO") ? atoi(getenv("DIAGAN_WINO")) : 1;
-  static const int wg_env = getenv("DIAGAN_WINO_WGRAD") ? atoi(getenv("DIAGAN_WINO_WGRAD")) : 1;
-  const int sw = diagan_conv_gemm_get_wino();
-  const int on = sw >= 0 ? sw : wino_env;
-  return on && wg_env &&
+  return kWino.get(-1, diagan_conv_gemm_get_wino()) && kWinoWgrad.env() &&
          wgrad_wino_supported(Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up, Kp);
 }
 
@@ -861,8 +858,8 @@ DIAGAN_API int diagan_conv_wgrad_splits(int M, int Co, int Kp) {
   // divides the 512 slots well (9, 18, 36, 72 tiles: 504 blocks); tile counts that do not (144 tiles: 3 splits fill
   // only 432 slots) are better served by a few FULL rounds -- 7 splits, 1008 blocks, 2 rounds: measured
   // 5.8 -> 5.0 ms at M=131072, Co=512, K=4608.  (A second, nearly empty round is what this model prices out.)
-  static const int min_steps = getenv("DIAGAN_WGRAD_MINSTEPS") ? atoi(getenv("DIAGAN_WGRAD_MINSTEPS")) : 4;
-  static const double fixed = getenv("DIAGAN_WGRAD_FIXED") ? atof(getenv("DIAGAN_WGRAD_FIXED")) : 6.0;
+  const int min_steps = kWgradMinSteps.env();
+  const double fixed = kWgradFixed.env();
   int smax = total_steps / min_steps;               // at least min_steps K-steps per split
   if (smax > 256) smax = 256;
   int splits = 1;

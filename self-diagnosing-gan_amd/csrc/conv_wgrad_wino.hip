@@ -369,14 +369,7 @@ int launch_wgrad_wino(WgradArgs a, int splits, int segments, hipStream_t st) {
   a.steps_per_split = cdiv(a.seg_steps, a.splits_per_seg);
   a.tiles = cdiv(g.Co, 64) * cdiv(g.Ci, 64);
   const int wgs = a.tiles * splits;
-  int rc;
-  switch (a.pro_mode) {
-    case PRO_NONE: rc = launch_gw<PRO_NONE>(a, wgs, st); break;
-    case PRO_RELU: rc = launch_gw<PRO_RELU>(a, wgs, st); break;
-    case PRO_AFFINE_RELU: rc = launch_gw<PRO_AFFINE_RELU>(a, wgs, st); break;
-    case PRO_LRELU: rc = launch_gw<PRO_LRELU>(a, wgs, st); break;
-    default: rc = launch_gw<PRO_AFFINE>(a, wgs, st); break;
-  }
+  const int rc = with_pro(a.pro_mode, [&](auto pro) { return launch_gw<decltype(pro)::value>(a, wgs, st); });
   if (rc != DIAGAN_OK) return rc;
   return check_launch("conv_wgrad_wino");
 }
@@ -416,14 +409,7 @@ int launch_wgrad_wino_batched(const WgradArgs* jobs, const int* splits, const in
     wgs += (b.cnt[j] + 7) & ~7;
   }
   for (int j = n; j < GW_BATCH_MAX; ++j) b.blk0[j] = wgs, b.cnt[j] = 0;
-  int rc;
-  switch (jobs[0].pro_mode) {
-    case PRO_NONE: rc = launch_gw_batched<PRO_NONE>(b, wgs, st); break;
-    case PRO_RELU: rc = launch_gw_batched<PRO_RELU>(b, wgs, st); break;
-    case PRO_AFFINE_RELU: rc = launch_gw_batched<PRO_AFFINE_RELU>(b, wgs, st); break;
-    case PRO_LRELU: rc = launch_gw_batched<PRO_LRELU>(b, wgs, st); break;
-    default: rc = launch_gw_batched<PRO_AFFINE>(b, wgs, st); break;
-  }
+  const int rc = with_pro(jobs[0].pro_mode, [&](auto pro) { return launch_gw_batched<decltype(pro)::value>(b, wgs, st); });
   if (rc != DIAGAN_OK) return rc;
   return check_launch("conv_wgrad_wino_batched");
 }

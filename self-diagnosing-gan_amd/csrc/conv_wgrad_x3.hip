@@ -21,6 +21,7 @@
 // Split-K over pixels, slabs and the deterministic second-stage sum exactly as conv_wgrad.hip (same WgradArgs, same grid).
 // Roofline: bf16 MFMA (dense 2.5 PFLOP/s / 6 products = 416.7 TFLOP/s fp32-equivalent).
 #include "conv_common.h"
+#include "switches.h"
 #include "wino_weights.h"
 #include <stdlib.h>
 
@@ -205,10 +206,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradArgs a
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 static int wgrad_x3_switch = -1;     // process-level diagnostic switch (-1: the environment's DIAGAN_WGRAD_X3, default on)
 void wgrad_x3_set(int on) { wgrad_x3_switch = on; }
-static bool wgrad_x3_enabled() {
-  static const int env = getenv("DIAGAN_WGRAD_X3") ? atoi(getenv("DIAGAN_WGRAD_X3")) : 1;
-  return (wgrad_x3_switch >= 0 ? wgrad_x3_switch : env) != 0;
-}
+static bool wgrad_x3_enabled() { return kWgradX3.get(-1, wgrad_x3_switch) != 0; }
 
 // the launches this kernel takes from conv_wgrad_kernel<128,128,PRO_NONE,*>: whole 128 x 128 tiles, whole 32-channel blocks of a tap per
 // eight lanes, no prologue, no bias column, and enough work that the matrix pipe -- not the launch -- is what the time goes to
@@ -218,8 +216,7 @@ bool wgrad_x3_takes(const WgradArgs& a, bool x3_on) {
   if (a.pro_mode != PRO_NONE || a.bias_off >= 0 || g.up != 1) return false;
   if ((g.Co & 127) || (g.Kp & 127) || g.K != g.Kp || (g.Ci & 31)) return false;
   if (wgrad_x3_switch == 2) return true;             // (tests: every geometry the kernel can run)
-  static const double floor_mac = getenv("DIAGAN_WGRAD_X3_MIN_MAC") ? atof(getenv("DIAGAN_WGRAD_X3_MIN_MAC")) : 4e9;
-  return (double)a.M * g.Co * g.K >= floor_mac;
+  return (double)a.M * g.Co * g.K >= kWgradX3MinMac.env();
 }
 
 static bool wgrad_x3_nopad(const ConvGeom& g) {

@@ -582,13 +582,7 @@ int launch_wino(ConvGemmArgs a, float* ws, hipStream_t st) {
   a.dWo = make_fastdiv((unsigned)(g.Wo >> 1));
   a.dHo = make_fastdiv((unsigned)(g.Ho >> 1));
   const float* ug = launch_wino_weights(a.w, ws, g.Co, g.Ci, g.Kp, g.dr < 0 ? 1 : 0, st);
-  switch (a.pro_mode) {
-    case PRO_NONE: return launch_wino_pro<PRO_NONE>(a, ug, st);
-    case PRO_RELU: return launch_wino_pro<PRO_RELU>(a, ug, st);
-    case PRO_AFFINE_RELU: return launch_wino_pro<PRO_AFFINE_RELU>(a, ug, st);
-    case PRO_LRELU: return launch_wino_pro<PRO_LRELU>(a, ug, st);
-    default: return launch_wino_pro<PRO_AFFINE>(a, ug, st);
-  }
+  return with_pro(a.pro_mode, [&](auto pro) { return launch_wino_pro<decltype(pro)::value>(a, ug, st); });
 }
 
 }  // namespace diagan

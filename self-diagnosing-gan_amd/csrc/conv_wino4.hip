@@ -27,6 +27,7 @@
 //
 // Roofline: MFMA fp32; the kernel executes 36/144 of the direct convolution's multiply-accumulates.
 #include "conv_common.h"
+#include "switches.h"
 #include <type_traits>
 #include "wino_weights.h"
 
@@ -1338,11 +1339,7 @@ static int launch_wino4_pro(const ConvGemmArgs& a, const float* ug, hipStream_t 
 static int g_wino4x = -1;
 void wino4_set_x3(int mode) { g_wino4x = mode; }
 int call_opt_wino4x();                             // conv_gemm.hip: the current call's option (-1: none)
-int wino4_get_x3() {
-  static const int env = getenv("DIAGAN_WINO4_X3") ? atoi(getenv("DIAGAN_WINO4_X3")) : 0;
-  const int c = call_opt_wino4x();
-  return c >= 0 ? c : (g_wino4x >= 0 ? g_wino4x : env);
-}
+int wino4_get_x3() { return kWino4X3.get(call_opt_wino4x(), g_wino4x); }
 // floats of workspace the transformed weights need (with X3 enabled: room for the split format, 6 instead of 4 bytes per element)
 static long x3_floats(long fp32_floats) { return wino4_get_x3() > 0 ? fp32_floats + fp32_floats / 2 : fp32_floats; }
 long wino4_ws_floats(int Co, int Ci) { return x3_floats((long)cdiv(Co, W4N) * W4N * Ci * 36); }
@@ -1405,30 +1402,23 @@ static int wino4_ksplit_impl(int B, int Ho, int Wo, int Ci, int Co, int allow_sp
   return 0;
 }
 
-// `a` as prepared by diagan_conv_gemm (dWo / dHo re-made here for the TILE grid); ws: wino4_ws_floats(Co, Ci) floats
+// the launch preamble of the four launch_wino4* below: dWo / dHo re-made for the grid of 4x4 TILES; returns a's geometry
+static const ConvGeom& wino4_tile_grid(ConvGemmArgs& a) {
+  a.dWo = make_fastdiv((unsigned)(a.g.Wo >> 2));
+  a.dHo = make_fastdiv((unsigned)(a.g.Ho >> 2));
+  return a.g;
+}
+
+// `a` as prepared by diagan_conv_gemm; ws: wino4_ws_floats(Co, Ci) floats
 int launch_wino4(ConvGemmArgs a, float* ws, hipStream_t st) {
-  const ConvGeom& g = a.g;
-  a.dWo = make_fastdiv((unsigned)(g.Wo >> 2));
-  a.dHo = make_fastdiv((unsigned)(g.Ho >> 2));
+  const ConvGeom& g = wino4_tile_grid(a);
   const long f32 = (long)cdiv(g.Co, W4N) * W4N * g.Ci * 36;
   if (wino4_x3_ok(a)) {
     const float* ug = wino4_weights<0>(a, ws, g.dr < 0 ? 1 : 0, 1.f, f32 + f32 / 2, st, true);
-    switch (a.pro_mode) {
-      case PRO_NONE: return launch_wino4_pro<PRO_NONE, 0, true>(a, ug, st);
-      case PRO_RELU: return launch_wino4_pro<PRO_RELU, 0, true>(a, ug, st);
-      case PRO_AFFINE_RELU: return launch_wino4_pro<PRO_AFFINE_RELU, 0, true>(a, ug, st);
-      case PRO_LRELU: return launch_wino4_pro<PRO_LRELU, 0, true>(a, ug, st);
-      default: return launch_wino4_pro<PRO_AFFINE, 0, true>(a, ug, st);
-    }
+    return with_pro(a.pro_mode, [&](auto pro) { return launch_wino4_pro<decltype(pro)::value, 0, true>(a, ug, st); });
   }
   const float* ug = wino4_weights<0>(a, ws, g.dr < 0 ? 1 : 0, 1.f, f32, st);
-  switch (a.pro_mode) {
-    case PRO_NONE: return launch_wino4_pro<PRO_NONE>(a, ug, st);
-    case PRO_RELU: return launch_wino4_pro<PRO_RELU>(a, ug, st);
-    case PRO_AFFINE_RELU: return launch_wino4_pro<PRO_AFFINE_RELU>(a, ug, st);
-    case PRO_LRELU: return launch_wino4_pro<PRO_LRELU>(a, ug, st);
-    default: return launch_wino4_pro<PRO_AFFINE>(a, ug, st);
-  }
+  return with_pro(a.pro_mode, [&](auto pro) { return launch_wino4_pro<decltype(pro)::value>(a, ug, st); });
 }
 
 // tile_cfg 11 / 12 on the F(4x4) kernel (MODE 1 / 2): convolution + 2x2 average pool in 25 products per 4x4 tile, and its data
@@ -1436,31 +1426,24 @@ int launch_wino4(ConvGemmArgs a, float* ws, hipStream_t st) {
 // Taken where the launch fills the chip (>= 192 workgroups of 32 tiles x 64 channels, no channel split) and H, W are
 // multiples of 4; DIAGAN_WINO4_POOL=0 keeps the F(2x2) pooled kernels; force: any launch size (diagan_conv_gemm_set_wino4(2), tests).
 bool wino4_pool_ok(int B, int Ho, int Wo, int Ci, int Co, long ws_floats, bool force) {
-  static const int env = getenv("DIAGAN_WINO4_POOL") ? atoi(getenv("DIAGAN_WINO4_POOL")) : 1;
-  static const int w4 = getenv("DIAGAN_WINO4") ? atoi(getenv("DIAGAN_WINO4")) : 1;
-  static const int min_wgs = getenv("DIAGAN_WINO4_POOL_MIN_WGS") ? atoi(getenv("DIAGAN_WINO4_POOL_MIN_WGS")) : 192;
-  if (!env || !w4 || !wino4_geom_ok(Ho, Wo, Ci) || (Co & 3) || Ci < 32) return false;
+  if (!kWino4Pool.env() || !kWino4.env() || !wino4_geom_ok(Ho, Wo, Ci) || (Co & 3) || Ci < 32) return false;
   const long wgs = (long)cdiv((long)B * (Ho >> 2) * (Wo >> 2), W4T) * cdiv(Co, W4N);
-  return (force || wgs >= min_wgs) && x3_floats((long)cdiv(Co, W4N) * W4N * Ci * 28) <= ws_floats;      // 56 units x 256 floats per 8 channels and column block
+  return (force || wgs >= kWino4PoolMinWgs.env()) && x3_floats((long)cdiv(Co, W4N) * W4N * Ci * 28) <= ws_floats;      // 56 units x 256 floats per 8 channels and column block
 }
 
 int launch_wino4_pool(ConvGemmArgs a, float* ws, hipStream_t st) {
-  const ConvGeom& g = a.g;
-  a.dWo = make_fastdiv((unsigned)(g.Wo >> 2));
-  a.dHo = make_fastdiv((unsigned)(g.Ho >> 2));
+  const ConvGeom& g = wino4_tile_grid(a);
   const float* ug = wino4_weights<1>(a, ws, 0, 1.f, (long)cdiv(g.Co, W4N) * W4N * g.Ci * 28, st);
 #if W4_ULOAD && W4_ULOAD_POOLED
   const int left = (g.Ci / W4K) % 3;          // (no channel split in the pooled modes: the K loop is Ci / 8 steps)
-  if (left == 1) return a.pro_mode == PRO_RELU ? launch_wino4_pro<PRO_RELU, 1, false, 1>(a, ug, st) : launch_wino4_pro<PRO_NONE, 1, false, 1>(a, ug, st);
-  if (left == 2) return a.pro_mode == PRO_RELU ? launch_wino4_pro<PRO_RELU, 1, false, 2>(a, ug, st) : launch_wino4_pro<PRO_NONE, 1, false, 2>(a, ug, st);
+  if (left == 1) return with_pro_relu(a.pro_mode, [&](auto pro) { return launch_wino4_pro<decltype(pro)::value, 1, false, 1>(a, ug, st); });
+  if (left == 2) return with_pro_relu(a.pro_mode, [&](auto pro) { return launch_wino4_pro<decltype(pro)::value, 1, false, 2>(a, ug, st); });
 #endif
-  return a.pro_mode == PRO_RELU ? launch_wino4_pro<PRO_RELU, 1>(a, ug, st) : launch_wino4_pro<PRO_NONE, 1>(a, ug, st);
+  return with_pro_relu(a.pro_mode, [&](auto pro) { return launch_wino4_pro<decltype(pro)::value, 1>(a, ug, st); });
 }
 
 int launch_wino4_unpool(ConvGemmArgs a, float* ws, hipStream_t st) {
-  const ConvGeom& g = a.g;
-  a.dWo = make_fastdiv((unsigned)(g.Wo >> 2));
-  a.dHo = make_fastdiv((unsigned)(g.Ho >> 2));
+  const ConvGeom& g = wino4_tile_grid(a);
   const float* ug = wino4_weights<1>(a, ws, 1, 1.f, (long)cdiv(g.Co, W4N) * W4N * g.Ci * 28, st);
 #if W4_ULOAD && W4_ULOAD_POOLED
   const int left = (g.Ci / W4K) % 3;
@@ -1475,9 +1458,7 @@ int launch_wino4_unpool(ConvGemmArgs a, float* ws, hipStream_t st) {
 // Taken where the plain F(4x4) launch of the same convolution would be (wino4_ksplit == 1: >= 192 workgroups that fill their
 // rounds at least as well as the F(2x2) kernel's); DIAGAN_WINO4_UPIN=0: off; force: any launch size (tests).
 bool wino4_upin_ok(int B, int Ho, int Wo, int Ci, int Co, long ws_floats, bool force) {
-  static const int env = getenv("DIAGAN_WINO4_UPIN") ? atoi(getenv("DIAGAN_WINO4_UPIN")) : 1;
-  static const int w4 = getenv("DIAGAN_WINO4") ? atoi(getenv("DIAGAN_WINO4")) : 1;
-  if (!env || !w4 || !wino4_geom_ok(Ho, Wo, Ci) || (Co & 3) || wino4_ws_floats(Co, Ci) > ws_floats) return false;
+  if (!kWino4Upin.env() || !kWino4.env() || !wino4_geom_ok(Ho, Wo, Ci) || (Co & 3) || wino4_ws_floats(Co, Ci) > ws_floats) return false;
   // (the alternative is the F(2x2) kernel AFTER a separate up-sampling pass over a 4x larger tensor, and this mode's lighter
   //  loader runs 1.1x the plain F(4x4) convolution: the bar against F(2x2) is lower than for the plain convolution --
   //  SNGAN-64's stacked block2.c1, 384 workgroups = 1.5 rounds against F(2x2)'s exact 3, qualifies)
@@ -1485,28 +1466,14 @@ bool wino4_upin_ok(int B, int Ho, int Wo, int Ci, int Co, long ws_floats, bool f
 }
 
 int launch_wino4_upin(ConvGemmArgs a, float* ws, hipStream_t st) {
-  const ConvGeom& g = a.g;
-  a.dWo = make_fastdiv((unsigned)(g.Wo >> 2));
-  a.dHo = make_fastdiv((unsigned)(g.Ho >> 2));
+  const ConvGeom& g = wino4_tile_grid(a);
   const long f32 = (long)cdiv(g.Co, W4N) * W4N * g.Ci * 36;
   if (wino4_x3_ok(a)) {
     const float* ug = wino4_weights<0>(a, ws, 0, 0.0625f, f32 + f32 / 2, st, true);
-    switch (a.pro_mode) {
-      case PRO_NONE: return launch_wino4_pro<PRO_NONE, 3, true>(a, ug, st);
-      case PRO_RELU: return launch_wino4_pro<PRO_RELU, 3, true>(a, ug, st);
-      case PRO_AFFINE_RELU: return launch_wino4_pro<PRO_AFFINE_RELU, 3, true>(a, ug, st);
-      case PRO_LRELU: return launch_wino4_pro<PRO_LRELU, 3, true>(a, ug, st);
-      default: return launch_wino4_pro<PRO_AFFINE, 3, true>(a, ug, st);
-    }
+    return with_pro(a.pro_mode, [&](auto pro) { return launch_wino4_pro<decltype(pro)::value, 3, true>(a, ug, st); });
   }
   const float* ug = wino4_weights<0>(a, ws, 0, 0.0625f, f32, st);
-  switch (a.pro_mode) {
-    case PRO_NONE: return launch_wino4_pro<PRO_NONE, 3>(a, ug, st);
-    case PRO_RELU: return launch_wino4_pro<PRO_RELU, 3>(a, ug, st);
-    case PRO_AFFINE_RELU: return launch_wino4_pro<PRO_AFFINE_RELU, 3>(a, ug, st);
-    case PRO_LRELU: return launch_wino4_pro<PRO_LRELU, 3>(a, ug, st);
-    default: return launch_wino4_pro<PRO_AFFINE, 3>(a, ug, st);
-  }
+  return with_pro(a.pro_mode, [&](auto pro) { return launch_wino4_pro<decltype(pro)::value, 3>(a, ug, st); });
 }
 
 }  // namespace diagan

@@ -366,8 +366,8 @@ int launch_wino_pool(ConvGemmArgs a, float* ws, hipStream_t st) {
   a.dHo = make_fastdiv((unsigned)(g.Ho >> 1));
   const float* ug = launch_wino_weights(a.w, ws, g.Co, g.Ci, g.Kp, g.dr < 0 ? 1 : 0, st);
   if (g.Co % 128 == 0)
-    return a.pro_mode == PRO_RELU ? launch_wino_pool_pro<PRO_RELU, false, 2>(a, ug, st) : launch_wino_pool_pro<PRO_NONE, false, 2>(a, ug, st);
-  return a.pro_mode == PRO_RELU ? launch_wino_pool_pro<PRO_RELU, false, 1>(a, ug, st) : launch_wino_pool_pro<PRO_NONE, false, 1>(a, ug, st);
+    return with_pro_relu(a.pro_mode, [&](auto pro) { return launch_wino_pool_pro<decltype(pro)::value, false, 2>(a, ug, st); });
+  return with_pro_relu(a.pro_mode, [&](auto pro) { return launch_wino_pool_pro<decltype(pro)::value, false, 1>(a, ug, st); });
 }
 
 // tile_cfg 12: a.x is the HALF-resolution gradient [B][Ho/2][Wo/2][Ci]; y / mask_src / residual are full resolution

@@ -11,6 +11,7 @@
 // Reductions are two-stage with fp64 partials combined in a fixed order: deterministic, no atomics.
 // Roofline: HBM (each kernel reads its inputs once and writes its outputs once).
 #include "conv_common.h"
+#include "switches.h"
 
 namespace diagan {
 
@@ -676,11 +677,7 @@ static int colred_geometry(long M, int C, int* splits, int* rows_per_split, dim3
   const int C4 = C / 4;
   const int CW = C4 < 64 ? C4 : 64;
   const int gx = cdiv(C4, CW);
-  // a thread walks rows_per_split / (256 / columns) rows, four loads in flight: with 256 rows per split and 1024 blocks a
-  // 65536 x 256 reduction was 16 dependent iterations = 21 us; 128 / 2048: SNGAN-32 +0.8 %, SNGAN-64 +0.2 % end to end
-  // (64 / 4096: +1.0 % / -0.45 %; tools/probe/colred_sweep.sh)
-  static const int blocks = getenv("DIAGAN_COLRED_BLOCKS") ? atoi(getenv("DIAGAN_COLRED_BLOCKS")) : 2048;
-  static const int minrows = getenv("DIAGAN_COLRED_ROWS") ? atoi(getenv("DIAGAN_COLRED_ROWS")) : 128;
+  const int blocks = kColredBlocks.env(), minrows = kColredRows.env();      // (2048 / 128: measured, see switches.h)
   int s = cdiv(blocks, gx);                     // ~8 blocks per CU in total
   const long max_s = (M + minrows - 1) / minrows;           // at least 128 rows per split
   if (s > max_s) s = (int)max_s;

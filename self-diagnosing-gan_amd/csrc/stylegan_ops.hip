@@ -13,6 +13,7 @@
 // over the (iy, ix) whose kernel index is in range; the filter taps sit in LDS, lanes run along ox
 // (then minor) so global reads are coalesced.  Roofline: HBM (in read ~once through L2, out written once).
 #include "common.h"
+#include "switches.h"
 #include <stdlib.h>
 
 namespace diagan {
@@ -249,10 +250,7 @@ struct UpFirDnArgs {
 };
 
 // DIAGAN_FIR_ROWS=0: the one-output-row-per-lane form of the blur kernels (A/B; default: four rows per lane)
-static bool fir_rows() {
-  static const int env = getenv("DIAGAN_FIR_ROWS") ? atoi(getenv("DIAGAN_FIR_ROWS")) : 1;
-  return env != 0;
-}
+static bool fir_rows() { return diagan::kFirRows.env() != 0; }
 
 static __host__ __device__ __forceinline__ int floor_div_i(int a, int b) {
   int q = a / b;
