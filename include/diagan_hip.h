@@ -20,6 +20,7 @@
  */
 #ifndef DIAGAN_HIP_H
 #define DIAGAN_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -809,6 +810,26 @@ int diagan_poly_mmd_sums(const void* X, int x_f64, int Nx, int ldx, const void* 
                          void* stream);
 int diagan_is_ws(int N, int C, int splits);
 int diagan_is_scores(const float* logits, int N, int C, int ld, int splits, double* ws, double* out, void* stream);
+
+/* ---- nearest-row search (Inclusive GAN's get_min_latent_idxs, diagan-pkg/diagan/models/inclusive_gan.py:178-199), DESIGN §8i --
+ * nn_argmin: for every query row r of q [Nq][ldq], over the candidate rows j of c [Nc][ldc] (the first D columns of both),
+ *   t[r][j] = c_sqnorm[j] - 2 <q_r, c_j> is minimised; c_sqnorm is diagan_row_sqnorm of c.  The row term |q_r|^2 is constant in j
+ *   and left out (one rounding fewer): the squared distance is best_t[r] + |q_r|^2.  fp32 products and sums on the fp32 matrix
+ *   pipe; the Nq x Nc matrix is never stored.
+ *   accumulate == 0 writes best_t[r] = min_j t[r][j] and best_idx[r] = idx_offset + argmin_j.  accumulate == 1 merges with the
+ *   pair already in best_t / best_idx, replacing it only where the new minimum is strictly smaller: candidates may be fed in
+ *   chunks of ascending idx_offset.
+ *   Ties: among bit-equal values of t the lowest global index wins, whatever tiling or split the launch chose and whether the
+ *   candidates came in one call or several; best_t and best_idx are the same bits either way.  (The reference keeps the first
+ *   index inside a 64-wide chunk and lets the LATER chunk win between chunks: a rule that depends on its chunking.)
+ *   Precondition: every input value is finite and no t overflows.  Otherwise the result is unspecified (the indices stay inside
+ *   [idx_offset, idx_offset + Nc) or keep their earlier value).
+ *   ws: diagan_nn_argmin_ws(Nq, Nc) bytes, 4-byte aligned, owned by the caller; any D >= 1 and any ld >= D are accepted (rows
+ *   that are 16-byte aligned, i.e. aligned bases and ld % 4 == 0, are read four values at a time).  No float atomics.
+ * nn_argmin_ws: bytes of workspace for that shape; 0 when Nq <= 0 or Nc <= 0. */
+int diagan_nn_argmin(const float* q, int Nq, int ldq, const float* c, int Nc, int ldc, const float* c_sqnorm, int D, long idx_offset,
+                     int accumulate, float* best_t, long* best_idx, void* ws, void* stream);
+size_t diagan_nn_argmin_ws(int Nq, int Nc);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 The reference's `train_mimicry_phase1.py` (flags :29-51, per-dataset schedule :82-92, trainer wiring :104-126) and
 `train_mimicry_phase2.py` (flags :39-56, scorer call :87-93, weighted sampler :21-34, trainer wiring :128-153) keep
 their flag names, defaults and on-disk layout; the scripts of the same names at the repository root are two-line
-wrappers around `phase1()` / `phase2()` below.  Flags are declared as data (one table per phase plus the shared
+wrappers around `phase1()` / `phase2()` below (further down: the colour-MNIST phases and the Inclusive GAN baseline).  Flags are declared as data (one table per phase plus the shared
 ones) so that the contract is testable (`tests/test_host_logic.py` compares names and defaults).
 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N train_mimicry_phaseK.py ...` -- one process per GPU
@@ -338,5 +338,63 @@ def color_mnist_phase2(argv=None, dataset=None):
                          dataloader_drs=loader_drs, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
                          vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
                          device=run.device, save_logits=False, compat_fetch_quirk=args.compat_fetch_quirk)
+    trainer.train()
+    return trainer
+
+
+# ---- Inclusive GAN baseline (train_mimicry_inclusive.py: flags :46-68, trainer wiring :113-131) ------------------------------
+# The colour-MNIST phase-1 script with `inclusive=True`: the generator gets the loader and the dataset size.  The reference's
+# closing sample plot is left out, as in the other front ends.
+INCLUSIVE_FLAGS = [
+    (("--dataset", "-d"), "color_mnist", str, None),
+    (("--root", "-r"), "./dataset/colour_mnist", str, "dataset dir"),
+    (("--work_dir",), "./exp_results", str, "output dir"),
+    (("--exp_name",), "colour_mnist", str, "exp name"),
+    (("--loss_type",), "ns", str, "loss type"),
+    (("--model",), "mnist_dcgan", str, "network model"),
+    (("--gpu",), "0", str, "id(s) for CUDA_VISIBLE_DEVICES"),
+    (("--num_pack",), 1, int, None),
+    (("--batch_size",), 64, int, None),
+    (("--seed",), 1, int, None),
+    (("--use_clipping",), False, _FLAG, None),
+    (("--num_steps",), 20000, int, None),
+    (("--logit_save_steps",), 100, int, None),
+    (("--decay",), "None", str, None),
+    (("--n_dis",), 1, int, None),
+    (("--major_ratio",), 0.99, float, None),
+    (("--num_data",), 10000, int, None),
+    (("--topk",), 0, int, None),
+    (("--resample_score",), None, str, None),
+    # not in the reference
+    (("--num_workers",), 0, int, None),
+    (("--inception_weights",), None, str, "FID Inception-v3 weights file (default: the file named by DIAGAN_FID_WEIGHTS)"),
+    (("--latent_factor",), 10, int, "candidate latents per training image in the nearest-latent refresh"),
+]
+
+
+def inclusive_parser():
+    return make_parser(INCLUSIVE_FLAGS)
+
+
+def inclusive(argv=None, dataset=None, inception=None):
+    """`inception`: a ready InceptionV3 or weights object in place of --inception_weights (tests)."""
+    args = inclusive_parser().parse_args(argv)
+    run = _Run(args)
+    if run.world > 1:
+        raise NotImplementedError("train_mimicry_inclusive.py is single-GPU, as in the reference")
+    train_set = get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
+                                       major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
+    loader = _plain_weighted_loader(train_set, args.batch_size, args.num_workers)
+    netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, num_pack=args.num_pack,
+                                           loss_type=args.loss_type, topk=args.topk == 1, inclusive=True,
+                                           num_data=args.num_data, dataloader=loader,
+                                           inception=inception if inception is not None else args.inception_weights,
+                                           latent_factor=args.latent_factor)
+    print_num_params(netG, netD)
+    print(args)
+    trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
+                         optD=optD, optG=optG, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
+                         vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
+                         device=run.device, topk=args.topk, save_logits=args.num_pack == 1, save_eval_logits=False)
     trainer.train()
     return trainer

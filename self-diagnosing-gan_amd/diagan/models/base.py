@@ -149,11 +149,10 @@ class BaseGenerator(BaseModel):
         errG, _ = E.loss_gen(output.detach().contiguous(), self.loss_type, k=k, need_grad=False)
         return errG[0]
 
-    def train_step(self, real_batch, netD, optG, log_data, device=None, global_step=None, scaler=None, noise=None,
-                   **kwargs):
-        """One G update (restated base step, topk_models.py:46-116 / mnist.py:82-152)."""
-        if scaler is not None:
-            raise NotImplementedError("amp/GradScaler is not part of the fp32 MI355X path")
+    def adversarial_grads(self, real_batch, netD, optG, device=None, noise=None):
+        """The G update up to, and without, optG.step(): draws z, runs G and D forward and backward and leaves the (reduced)
+        gradients of the adversarial loss in the parameters' .grad.  Returns errG as a [1] device tensor.  train_step below is
+        this plus the optimiser step; a subclass with work between the two (models/inclusive_gan.py) calls it as well."""
         self.zero_grad()
         self.wgrad_batch.hold = _world_size() > 1      # the weight-gradient reduction overlaps the exchange (sync_grads)
         batch_size = real_batch[0].shape[0]
@@ -168,6 +167,14 @@ class BaseGenerator(BaseModel):
         g_img = netD.backward_nhwc(dctx, dlogit, need_wgrad=False, need_gx=True)
         self.backward_nhwc(gctx, g_img)
         self.sync_grads(optG)
+        return errG
+
+    def train_step(self, real_batch, netD, optG, log_data, device=None, global_step=None, scaler=None, noise=None,
+                   **kwargs):
+        """One G update (restated base step, topk_models.py:46-116 / mnist.py:82-152)."""
+        if scaler is not None:
+            raise NotImplementedError("amp/GradScaler is not part of the fp32 MI355X path")
+        errG = self.adversarial_grads(real_batch, netD, optG, device=device, noise=noise)
         optG.step()
         log_data.add_metric('errG', errG[0], group='loss')
         return log_data

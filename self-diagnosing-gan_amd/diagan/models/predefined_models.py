@@ -5,8 +5,10 @@
 architecture trained with the 'ns' loss.  Architectures and Adam settings per dataset are the reference's; they are
 declared as data below, and the per-dataset helpers of the reference (`get_cifar10_gen`, ...) are generated from the
 table.  Optimisers are `FusedAdam` (one launch per step over the network's flat parameter slab).  'ffhq' builds the StyleGAN2 pair at 256^2
-(reference :153-163; extra keywords -- loss_type, gold, ... -- are swallowed by the classes' **kwargs as there).  Model
-families outside the accelerated path (infomax_gan, ssgan, toy, inclusive) raise NotImplementedError."""
+(reference :153-163; extra keywords -- loss_type, gold, ... -- are swallowed by the classes' **kwargs as there).
+`inclusive=True` builds the Inclusive GAN generator (models/inclusive_gan.py) for 'color_mnist' and, with nc=1, for
+'mnist_fmnist'; it needs `dataloader` and `num_data` (or `dataset`), which the discriminators' **kwargs swallow.  Model
+families outside the accelerated path (infomax_gan, ssgan, toy) raise NotImplementedError."""
 from diagan.optim import FusedAdam
 
 
@@ -37,9 +39,11 @@ RECIPES = {
                    disc_gold=_named('diagan.models.gold_reweight_models', 'GoldSNGANDiscriminator64')),
     'color_mnist': dict(family='mnist_dcgan', adam=(1e-4, (0.5, 0.9)), fixed={},
                         gen=_named('diagan.models.mnist', 'MNIST_DCGAN_Generator'),
+                        gen_inclusive=_named('diagan.models.inclusive_gan', 'InclusiveMNISTDCGANGenerator'),
                         disc=_named('diagan.models.mnist', 'MNIST_DCGAN_Discriminator')),
     'mnist_fmnist': dict(family='mnist_dcgan', adam=(1e-4, (0.5, 0.9)), fixed=dict(nc=1),
                          gen=_named('diagan.models.mnist', 'MNIST_DCGAN_Generator'),
+                         gen_inclusive=_named('diagan.models.inclusive_gan', 'InclusiveMNISTDCGANGenerator'),
                          disc=_named('diagan.models.mnist', 'MNIST_DCGAN_Discriminator')),
     'ffhq': dict(family='stylegan', adam=(2e-4, (0.0, 0.9)), fixed=dict(size=256),
                  gen=_named('diagan.models.stylegan2', 'StyleGANGenerator'),
@@ -72,9 +76,10 @@ def build_generator(dataset_name, model='sngan', loss_type='hinge', gold=False, 
         netG = recipe['gen_topk']()(loss_type=loss_type, topk=topk, **kwargs) if topk else \
             recipe['gen']()(loss_type=loss_type, **kwargs)
     else:
-        if kwargs.get('inclusive'):
-            raise NotImplementedError("InclusiveMNISTDCGANGenerator is a baseline outside the hot path (SURVEY §2)")
-        netG = recipe['gen']()(loss_type=loss_type, topk=topk, **recipe['fixed'], **kwargs)
+        # inclusive=True: the Inclusive GAN baseline (reference predefined_models.py:101-106,127-132); num_data / dataset,
+        # dataloader and the keyword-only extras (inception, latent_factor) travel in **kwargs
+        gen = recipe['gen_inclusive' if kwargs.get('inclusive') else 'gen']()
+        netG = gen(loss_type=loss_type, topk=topk, **recipe['fixed'], **kwargs)
     return netG, _optimizer(netG, recipe)
 
 

@@ -273,6 +273,8 @@ class LogTrainer:
         if env == "0" or self.world > 1 or self.topk or self.gold or self.device.type != 'cuda':
             return False
         nets = [n for n in (self.netG, self.netD, self.netD_drs) if n is not None]
+        if not all(getattr(n, 'graph_capturable', True) for n in nets):      # a step with host control flow (Inclusive GAN: it
+            return False                                                    # reads a loader and branches on global_step)
         return env == "1" or all(getattr(n, 'launch_bound', False) for n in nets)
 
     def _graphed_updates(self, step, batches, batches_drs):
