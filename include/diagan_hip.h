@@ -17,6 +17,15 @@
  *   - activations are NHWC fp32 ("pixels x channels" row-major), channel counts padded to a
  *     multiple of 4; weights are consumed in the packed GEMM layouts produced by
  *     diagan_pack_weights / diagan_pack_oihw / diagan_pack_batched (see DESIGN.md "Data layout in HBM").
+ *
+ * This file is also the Python binding: diagan/_native reads the ctypes argtypes / restype of every entry point from the
+ * prototypes below (comments and preprocessor lines removed), so a declaration has to stay in this form:
+ *   - one prototype `RET diagan_name(params);` per exported function, `(void)` for none; no macros in it, no function pointers,
+ *     no arrays or structs by value;
+ *   - RET is int, int64_t, size_t or const char*;
+ *   - a parameter is an int, float, double, int64_t or long, or a pointer (of any depth, const or not) to one of those, to
+ *     unsigned long long, to void, or to a struct declared here -- every pointer is bound as void*.
+ * Anything else fails when the header is read, with the declaration's name (tests/test_native_abi.py).
  */
 #ifndef DIAGAN_HIP_H
 #define DIAGAN_HIP_H

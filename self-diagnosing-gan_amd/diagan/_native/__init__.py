@@ -7,37 +7,72 @@ diagan-pkg/diagan/models/op/fused_bias_act.cpp:7,13-14).
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DIAGAN_LIB_PATH: another build of the same library (kernel A/B runs of the tuning tools); default: the in-tree build
 LIB_PATH = os.environ.get("DIAGAN_LIB_PATH") or os.path.join(_HERE, "libdiagan_hip.so")
 
+# include/diagan_hip.h, two levels above the package: the tree is used from a checkout, there is no installed copy
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(_HERE))), "include", "diagan_hip.h")
+
 _lib = None
 
-c_void_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_i64 = ctypes.c_int64
-c_f32 = ctypes.c_float
-c_f64 = ctypes.c_double
-
-# name -> argtypes (restype is int unless listed in _RESTYPE)
-_SIGS = {
-    "diagan_abi_version": [],
-    "diagan_ldr_scores_f64": [c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_int, c_void_p, c_f64, c_f64, c_void_p, c_void_p],
-    "diagan_ldr_scores_f32": [c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_int, c_void_p, c_f32, c_f32, c_void_p, c_void_p],
-    "diagan_logit_scatter": [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p],
-}
-_RESTYPE = {
-    "diagan_last_error": ctypes.c_char_p,
-    "diagan_target_arch": ctypes.c_char_p,
-}
+# The binding table IS the header: every `RET diagan_name(params);` prototype of include/diagan_hip.h, whose opening comment
+# states the grammar.  A pointer parameter of any kind is a c_void_p (callers pass data_ptr() integers, None or ctypes.byref).
+_PARAMS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64,
+           "long": ctypes.c_long}
+_RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_PROTOTYPE = re.compile(r"(?:^|[;{}])([^;{}()]*?)\b(diagan_\w+)\s*\(([^()]*)\)\s*(?=;)")
 
 
-def register(name, argtypes):
-    """Used by the op modules to declare further entry points before first use."""
-    _SIGS[name] = argtypes
+def _param(text, name):
+    if re.fullmatch(r"[\w\s*]+", text):                           # no arrays, no function pointers
+        if "*" in text:
+            return ctypes.c_void_p
+        words = [w for w in text.split() if w != "const"]
+        for typ in (" ".join(words), " ".join(words[:-1])):       # without and with a parameter name
+            if typ in _PARAMS:
+                return _PARAMS[typ]
+    raise ValueError(f"{name}: parameter type of '{text.strip()}' is not one the binding knows")
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) of every prototype in the text of a header; ValueError on a type outside the table."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    sigs = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise ValueError(f"{name}: return type '{ret}' is not one the binding knows")
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = (_RETURNS[ret], [_param(p, name) for p in params])
+    unread = sorted(set(re.findall(r"\b(diagan_\w+)\s*\(", text)) - set(sigs))
+    if unread:
+        raise ValueError(f"{unread[0]}: not a plain `RET name(params);` prototype")
+    return sigs
+
+
+_sigs = None
+
+
+def signatures():
+    """The table of the checkout's header, read once at first use."""
+    global _sigs
+    if _sigs is None:
+        if not os.path.exists(HEADER_PATH):
+            raise RuntimeError(f"diagan_hip.h not found at {HEADER_PATH}: the ctypes signatures are read from it "
+                               "(the package runs from a checkout of the repository).")
+        with open(HEADER_PATH) as f:
+            _sigs = parse_header(f.read())
+    return _sigs
+
+
+def _bind(L, name):
+    f = getattr(L, name)
+    f.restype, f.argtypes = signatures()[name]
+    return f
 
 
 def lib():
@@ -55,9 +90,8 @@ def lib():
         # process).  With torch's runtime already mapped, the DT_NEEDED entry resolves to it and there is exactly one.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, rt in _RESTYPE.items():
-            getattr(L, name).restype = rt
-            getattr(L, name).argtypes = []
+        for name in ("diagan_last_error", "diagan_target_arch"):     # also reached as attributes of the handle
+            _bind(L, name)
         _lib = L
     return _lib
 
@@ -68,10 +102,7 @@ _bound = {}
 def fn(name):
     f = _bound.get(name)
     if f is None:
-        L = lib()
-        f = getattr(L, name)
-        f.argtypes = _SIGS[name]
-        f.restype = ctypes.c_int
+        f = _bind(lib(), name)
         _bound[name] = f
     return f
 

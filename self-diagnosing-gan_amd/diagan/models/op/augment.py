@@ -23,12 +23,7 @@ from diagan import _native as nat
 __all__ = ['SYM6', 'AdaptiveAugment', 'sample_affine', 'sample_color', 'get_padding', 'augment_padding', 'augment',
            'apply_augment']
 
-P, I = nat.c_void_p, nat.c_int
-nat.register("diagan_augment_params", [])
 N_PARAMS = 18         # float64 per sample in the launches' parameter table (diagan_augment_params())
-nat.register("diagan_augment_workspace", [I, I, I, I, I, I, I, I, P])
-nat.register("diagan_augment_forward", [P, P, I, I, I, I, I, I, I, P, P, P])
-nat.register("diagan_augment_backward", [P, P, I, I, I, I, I, I, I, P, P, P])
 
 # Symlet-6 low-pass filter, the anti-aliasing kernel of the reference (non_leaking.py SYM6)
 SYM6 = (0.015404109327027373, 0.0034907120842174702, -0.11799011114819057, -0.048311742585633, 0.4910559419267466,
@@ -265,7 +260,7 @@ def sample_params(G_inv, C, height, width, pads):
 # ---- the device map and its adjoint ---------------------------------------------------------------------------------------------
 def _launch(name, x, params, pads, out, backward):
     B, _, H, W = x.shape
-    ws_bytes = nat.c_i64(0)
+    ws_bytes = ctypes.c_int64(0)
     nat.call("diagan_augment_workspace", B, H, W, *pads, int(backward), ctypes.byref(ws_bytes))
     ws = torch.empty(ws_bytes.value // 4, dtype=torch.float32, device=x.device)
     nat.call(name, nat.ptr(x), nat.ptr(params), B, H, W, *pads, nat.ptr(out), nat.ptr(ws), nat.current_stream())

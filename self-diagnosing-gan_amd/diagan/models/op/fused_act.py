@@ -10,14 +10,6 @@ from torch.autograd import Function
 
 from diagan import _native as nat
 
-P, I, F32, I64 = nat.c_void_p, nat.c_int, nat.c_f32, nat.c_i64
-nat.register("diagan_fused_bias_act", [P, P, P, P, I64, I64, I, I, I, F32, F32, P])
-nat.register("diagan_rowdot_chunks", [I, I])
-nat.register("diagan_rowdot", [P, P, P, P, I, I, I, P])
-nat.register("diagan_styled_bias_act", [P, P, P, P, P, P, I, I, I, I, F32, F32, P])
-nat.register("diagan_styled_bias_act_bwd", [P, P, P, P, P, P, P, P, P, I, I, I, I, F32, F32, P])
-nat.register("diagan_styled_bias_act_bwd_finish", [P, P, P, P, P, P, I, I, I, P])
-
 import os as _os
 FUSED_BWD = _os.environ.get("DIAGAN_SG2_FUSED_BWD", "1") != "0"
 
@@ -53,7 +45,6 @@ def _fused_bwd(gy, y, x, demod, noise, slope, scale, need_gx=True):
     nat.call("diagan_styled_bias_act_bwd_finish", nat.ptr(wd), nat.ptr(wb), nat.ptr(ws), nat.ptr(gd), nat.ptr(gb), nat.ptr(gs),
              b, h * w, c, nat.current_stream())
     return gx, gd, gb, gs
-
 
 
 def fused_bias_act(input, bias, refer, act, grad, alpha, scale, bias_dim=1):
@@ -196,10 +187,6 @@ class _StyledAct(Function):
         gs = (gpre * noise).sum().reshape(1) if noise is not None and need[3] else None
         gb = gpre.sum((0, 1, 2)) if need[4] else None
         return gx, gd, None, gs, gb, None, None
-
-
-nat.register("diagan_styled_bias_act_mod", [P, P, P, P, P, P, P, P, I, I, I, I, F32, F32, P])
-nat.register("diagan_styled_bias_act_mod_bwd", [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F32, F32, P])
 
 
 class _StyledActMod(Function):

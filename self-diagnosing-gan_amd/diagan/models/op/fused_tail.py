@@ -22,13 +22,6 @@ from diagan import _native as nat
 from diagan.models.op import fused_act as FA
 from diagan.models.op.upfirdn2d import _LinearFIR, _Plan, upfirdn2d_nhwc
 
-P, I, F32, I64 = nat.c_void_p, nat.c_int, nat.c_f32, nat.c_i64
-nat.register("diagan_bias_act_fir", [P, P, P, P] + [I] * 10 + [F32, F32, P])
-nat.register("diagan_bias_act_gate_bwd", [P, P, P, P, P, I, I, I, F32, F32, P])
-nat.register("diagan_bias_act_add", [P, P, P, P, I64, I, F32, F32, P])
-nat.register("diagan_fir_gate_bwd", [P, P, P, P, P, P] + [I] * 10 + [F32, F32, P])
-nat.register("diagan_fir_styled_act", [P, P, P] + [I] * 10 + [P, P, P, P, P, I, F32, F32, P])
-
 FUSED_TAILS = os.environ.get("DIAGAN_SG2_FUSED_TAILS", "1") != "0"
 FUSED_GATE = os.environ.get("DIAGAN_SG2_FUSED_GATE", "1") != "0"      # the blur's adjoint + the activation's gate in one pass
 
@@ -161,8 +154,6 @@ def blur_styled_act(x, kernel, pad, demod=None, noise=None, strength=None, bias=
 
 
 # ---- the generator's ToRGB in one pass over its input ---------------------------------------------------------------------------------
-nat.register("diagan_torgb_fwd", [P, P, P, P, P, I, I, I, P])
-nat.register("diagan_torgb_bwd", [P, P, P, P, P, P, P, P, I, I, I, P])
 
 
 def torgb_ok(x):
@@ -227,7 +218,6 @@ def torgb(x, s, weight, bias, scale):
 
 
 # ---- a tensor that feeds a convolution AND a resampling filter: the filter's adjoint adds the other gradient on its way out -------------
-nat.register("diagan_upfirdn2d_add", [P, P, P, P] + [I] * 14 + [P])
 
 
 class _ForkFIR(Function):
@@ -267,8 +257,6 @@ def fork_fir(x, kernel, up=1, down=1, pad=(0, 0)):
 
 
 # ---- the discriminator's first layer (1x1 convolution from RGB + bias + leaky ReLU) in one write of its output --------------------------
-nat.register("diagan_fromrgb_fwd", [P, P, P, P, I, I, I, F32, F32, F32, P])
-nat.register("diagan_fromrgb_bwd", [P, P, P, P, P, P, I, I, I, F32, F32, F32, P])
 
 
 def fromrgb_ok(x, weight, bias):
@@ -331,10 +319,6 @@ def fromrgb(x, weight, bias, wscale, negative_slope=0.2, scale=2 ** 0.5):
 
 
 # ---- the small dense pieces of the modulated convolution as single launches (csrc/stylegan_dense.hip) ----------------------------------
-nat.register("diagan_small_linear_fwd", [P, P, P, P, I, I, I, F32, F32, P])
-nat.register("diagan_small_linear_bwd", [P, P, P, P, P, P, I, I, I, F32, F32, P])
-nat.register("diagan_demod_fwd", [P, P, P, P, I, I, I, I, F32, F32, P])
-nat.register("diagan_demod_bwd", [P, P, P, P, P, P, P, I, I, I, I, F32, P])
 
 FUSED_DENSE = os.environ.get("DIAGAN_SG2_FUSED_DENSE", "1") != "0"
 

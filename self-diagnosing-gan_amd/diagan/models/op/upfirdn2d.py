@@ -14,9 +14,6 @@ from torch.autograd import Function
 
 from diagan import _native as nat
 
-P, I = nat.c_void_p, nat.c_int
-nat.register("diagan_upfirdn2d", [P, P, P] + [I] * 14 + [P, P, P])
-
 
 def upfirdn2d_op(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1):
     if not input.is_cuda:

@@ -1,3 +1,2 @@
 """Python-side op wrappers over the C ABI (one module per kernel family)."""
-from diagan.ops import conv, diffconv, eltwise, inception, linalg64, metrics64, nn_search  # noqa: F401  (register the entry-point signatures)
-from diagan.models import op as _stylegan_ops  # noqa: F401
+from diagan.ops import conv, diffconv, eltwise, inception, linalg64, metrics64, nn_search  # noqa: F401

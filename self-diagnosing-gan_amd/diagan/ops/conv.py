@@ -7,69 +7,6 @@ import torch
 
 from diagan import _native as nat
 
-P, I, F, I64 = nat.c_void_p, nat.c_int, nat.c_f32, nat.c_i64
-nat.register("diagan_conv_gemm", [P, P, P, P, P, I, P, F, P, P, I, F, P, P, I] + [I] * 15 + [P, I64, P, I, P])
-nat.register("diagan_conv_gemm_pick_ksplit", [I, I, I, I])
-nat.register("diagan_conv_gemm_pick_cfg", [I, I, I, I])
-nat.register("diagan_conv_wino_supported", [I] * 12)
-nat.register("diagan_conv_gemm_set_wino", [I])
-nat.register("diagan_conv_gemm_get_wino", [])
-nat.register("diagan_conv_gemm_set_wino4", [I])
-nat.register("diagan_conv_gemm_set_splitk_fused", [I])
-nat.register("diagan_conv_gemm_set_splitk_tickets", [P, I64])
-nat.register("diagan_conv_gemm_next_opts", [P])
-nat.register("diagan_conv_gemm_pending_opts", [P])
-nat.register("diagan_conv_gemm_last_cfg", [])
-nat.register("diagan_conv_gemm_set_x3", [I])
-nat.register("diagan_conv_gemm_get_x3", [])
-nat.register("diagan_conv_gemm_set_x3b", [I])
-nat.register("diagan_conv_gemm_get_x3b", [])
-nat.register("diagan_conv_gemm_x3b_force_form", [I])
-nat.register("diagan_conv_gemm_out_map", [I] * 9)
-nat.register("diagan_conv_gemm_final_cfg", [I] * 15 + [I64] + [I] * 4)
-nat.register("diagan_conv_wgrad_batched", [P, I, P])
-nat.register("diagan_conv_wgrad_batch_max", [])
-nat.register("diagan_conv_wgrad_batch_class", [I] * 14)
-nat.register("diagan_conv_gemm_set_wino4x", [I])
-nat.register("diagan_conv_gemm_get_wino4x", [])
-nat.register("diagan_conv_wino4_pool_used", [I] * 5 + [I64])
-nat.register("diagan_conv_wino4_upin_supported", [I] * 13 + [I64, I])
-nat.register("diagan_conv_gemm_weights_hint", [P, I, I, F])
-nat.register("diagan_conv_gemm_last_weight_format", [P, P, P, P, P])
-nat.register("diagan_wino_weight_blocks", [I, I])
-nat.register("diagan_wino_weights_batched", [P, I, I, P])
-nat.register("diagan_conv_wgrad_uses_wino", [I] * 13)
-nat.register("diagan_conv_wgrad_splits_geom", [I] * 14)
-nat.register("diagan_conv_gemm_set_x3_pieces", [I])
-nat.register("diagan_conv_gemm_get_x3_pieces", [])
-nat.register("diagan_conv_wgrad_uses_x3", [I] * 15 + [I64])
-nat.register("diagan_conv_wgrad_set_x3", [I])
-nat.register("diagan_conv_gemm_pick_cfg_geom", [I] * 15 + [I64])
-nat.register("diagan_conv_gemm_pick_cfg_grouped", [I] * 15 + [I64, I])
-nat.register("diagan_conv_gemm_tile_rows", [I])
-nat.register("diagan_conv_wino_pool_supported", [I] * 14 + [I64])
-nat.register("diagan_conv_wino_unpool_supported", [I] * 13 + [I64])
-nat.register("diagan_conv_gemm_tile_cols", [I])
-nat.register("diagan_conv_gemm_set_stamp_buffer", [P, I64])
-nat.register("diagan_conv_gemm_tune", [I, I, I])
-nat.register("diagan_conv3x3_co4_supported", [I] * 8)
-nat.register("diagan_conv3x3_co4", [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P])
-nat.register("diagan_conv3x3_ci4_supported", [I] * 8)
-nat.register("diagan_conv3x3_ci4", [P, P, P, P, F, P, P, I, I, I, I, I, I, P])
-nat.register("diagan_conv3x3_co4_wgrad_supported", [I] * 8)
-nat.register("diagan_conv3x3_co4_wgrad_splits", [I, I])
-nat.register("diagan_conv3x3_co4_wgrad", [P, P, P, I64, I64, P, P, I, I, I, I, I, I, P])
-nat.register("diagan_conv_wgrad", [P, P, P, I, I, I64, I64, P, P, I] + [I] * 14 + [P])
-nat.register("diagan_pack_batched", [P, I, I, I, I, I, P])
-nat.register("diagan_wgrad_finish_batched", [P, I, I64, I, P])
-nat.register("diagan_wgrad_finish_block_elems", [I])
-nat.register("diagan_conv_wgrad_splits", [I, I, I])
-nat.register("diagan_wgrad_reduce", [P, I, I64, P, I, P, P, P])
-nat.register("diagan_sn_power_iter", [P, P, P, P, P, P, P, I, I, F, I, P])
-nat.register("diagan_sn_prepare_batched", [P, I, I, I, I, I, F, I, I, P])
-nat.register("diagan_pack_weights", [P, P, P, P, I, I, I, I, I, P])
-nat.register("diagan_sn_grad_fix", [P, P, I, P, P, P, P, I, I, I, P])
-
 PRO_NONE, PRO_RELU, PRO_AFFINE_RELU, PRO_LRELU, PRO_AFFINE = 0, 1, 2, 3, 4
 # weight gradients only: the gathered image is the (H+1) x (W+1) grid of 0.25 * 2x2 box sums of x / relu(x) (eltwise.boxsum2), summed by
 # the kernel's loader from the H x W tensor it is handed (csrc/conv_common.h)

@@ -22,10 +22,6 @@ import ctypes as _ct
 from diagan import _native as nat
 from diagan.ops import conv as K
 
-_P, _I, _F = nat.c_void_p, nat.c_int, nat.c_f32
-nat.register("diagan_pack_oihw", [_P, _F, _P, _P] + [_I] * 8 + [_P])
-nat.register("diagan_unpack_oihw", [_P, _F, _P] + [_I] * 6 + [_P])
-nat.register("diagan_parity_weights", [_P, _P, _P] + [_I] * 5 + [_P, _P, _I, _P])
 # weight preparation in one launch each (csrc/weight_prep.hip, round 6): scale + pack (+ the data-gradient operand), and the parity
 # classes' sub-kernels / their adjoint; DIAGAN_SG2_FUSED_PREP=0: the torch-op compositions of rounds 1-5
 FUSED_PREP = os.environ.get("DIAGAN_SG2_FUSED_PREP", "1") == "1"

@@ -1,39 +1,7 @@
 """HBM-bound layer ops, loss heads and Adam over the C ABI (csrc/elementwise.hip, train_ops.hip)."""
-import ctypes
-
 import torch
 
 from diagan import _native as nat
-
-P, I, F, I64 = nat.c_void_p, nat.c_int, nat.c_f32, nat.c_i64
-nat.register("diagan_nchw_to_nhwc", [P, P, I, I, I, I, I, P])
-nat.register("diagan_nhwc_to_nchw", [P, P, I, I, I, I, I, P])
-nat.register("diagan_tanh_fwd", [P, P, I64, P])
-nat.register("diagan_tanh_bwd", [P, P, P, I64, P])
-nat.register("diagan_colred_workspace", [I64, I])
-nat.register("diagan_bn_stats", [P, I64, I, P, P, F, F, P, P, I, P, P, P, P, P, P])
-nat.register("diagan_bn_stats_fused", [P, I, I64, I, P, P, F, F, P, P, P, P, P, P, I, P, I64, P])
-nat.register("diagan_bn_stats_fused_splits", [I, I, I])
-nat.register("diagan_bn_bwd", [P, P, I64, I, P, P, P, P, I, I, F, P, F, P, P, I, P, P, P, P, P])
-nat.register("diagan_act_fwd", [P, P, P, F, P, F, P, I64, I, P])
-nat.register("diagan_act_bwd", [P, P, F, P, F, P, I64, P])
-nat.register("diagan_linear1_bwd_input", [P, P, P, I, I, P])
-nat.register("diagan_linear1_fwd", [P, P, P, P, I, I, P])
-nat.register("diagan_linear1_wgrad", [P, P, P, P, I, I, P])
-nat.register("diagan_bn_stats_grouped", [P, I64, I, I, P, P, F, F, P, P, P, P, P, P, P, P])
-nat.register("diagan_colsum", [P, I64, I, P, I, P, P])
-nat.register("diagan_upsample2x", [P, P, I, I, I, I, I, P, P, I, P])
-nat.register("diagan_upsample2x_bwd", [P, P, I, I, I, I, P, P])
-nat.register("diagan_avgpool2", [P, P, I, I, I, I, P, I, P])
-nat.register("diagan_avgpool2_bwd", [P, P, I, I, I, I, P, P])
-nat.register("diagan_boxsum2", [P, P, I, I, I, I, I, P])
-nat.register("diagan_head_fwd", [P, P, P, P, I, P, P, P, I, I, I, P])
-nat.register("diagan_head_bwd", [P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, P])
-nat.register("diagan_add", [P, P, P, I64, P])
-nat.register("diagan_loss_dis", [P, I, P, I, I, I, P, P, P, P])
-nat.register("diagan_loss_gen", [P, I, I, I, P, P, P])
-nat.register("diagan_adam_step", [P, P, P, P, I64, F, F, F, F, F, F, F, P])
-nat.register("diagan_adam_step_dev", [P, P, P, P, I64, P, P])
 
 LOSS_TYPES = {'gan': 0, 'ns': 1, 'hinge': 2, 'wasserstein': 3}
 ptr, st = nat.ptr, nat.current_stream
@@ -58,10 +26,7 @@ def _workspace(dev, nbytes):
 
 
 def _colred_ws(dev, M, C, groups=1):
-    fn = nat.lib().diagan_colred_workspace
-    fn.restype = ctypes.c_int64
-    fn.argtypes = [ctypes.c_int64, ctypes.c_int]
-    return _workspace(dev, fn(M, C) * groups)
+    return _workspace(dev, nat.fn("diagan_colred_workspace")(M, C) * groups)
 
 
 def nchw_to_nhwc(x, Cp, out=None):

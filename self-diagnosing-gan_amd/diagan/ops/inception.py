@@ -9,13 +9,6 @@ from diagan import _native as nat
 
 __all__ = ['conv_kp', 'conv', 'pool3', 'global_avg', 'prep', 'POOL_MAX_S2', 'POOL_MAX_S1', 'POOL_AVG_S1']
 
-P, I, F = nat.c_void_p, nat.c_int, nat.c_f32
-nat.register("diagan_incep_conv_kp", [I, I, I])
-nat.register("diagan_incep_conv", [P, I, I, I, I, I, I, P, P, I, I, I, I, I, I, I, I, P, I, I, I, I, I, P])
-nat.register("diagan_incep_pool3", [P, I, I, I, I, I, I, P, I, I, I, I, I, P])
-nat.register("diagan_incep_gap", [P, I, I, I, P, P])
-nat.register("diagan_incep_prep", [P, I, I, I, I, P, I, I, I, F, F, P])
-
 POOL_MAX_S2, POOL_MAX_S1, POOL_AVG_S1 = 0, 1, 2     # max 3x3 s2 p0, max 3x3 s1 p1, avg 3x3 s1 p1 (count_include_pad=False)
 
 

@@ -11,19 +11,6 @@ from diagan import _native as nat
 
 __all__ = ['gemm', 'total', 'trace', 'symmetrize', 'scale_diag', 'sqrt_newton_schulz']
 
-P, I, L, F = nat.c_void_p, nat.c_int, nat.c_i64, nat.c_f64
-nat.register("diagan_gemm_f64", [P, P, P, I, I, I, I, I, I, I, F, F, F, P, P])
-nat.register("diagan_gemm_f64_tile", [])
-nat.register("diagan_sum_f64", [P, L, I, P, P])
-nat.register("diagan_trace_f64", [P, I, I, P, P])
-nat.register("diagan_sym_f64", [P, I, I, F, P])
-nat.register("diagan_scale_diag_f64", [P, P, I, I, F, F, P])
-nat.register("diagan_fid_term", [P, P, P, P, I, I, P, P])
-nat.register("diagan_feat_colsum_chunks", [I])
-nat.register("diagan_feat_moments", [P, I, I, I, I, P, P, P, P, P])
-nat.register("diagan_feat_center", [P, I, P, P, I, I, I, P, I, P])
-nat.register("diagan_moments_merge", [P, P, P, I, P, P, P, I, I, P])
-
 # Newton-Schulz stopping rule
 NS_TOL = 1e-15        # converged: |tr Y_k - tr Y_k-1| <= NS_TOL |tr Y_k|
 NS_SETTLED = 1e-10    # the change may only be read as "growing again" once it has fallen below NS_SETTLED |tr|

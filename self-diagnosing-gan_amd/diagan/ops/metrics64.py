@@ -8,12 +8,6 @@ from diagan import _native as nat
 
 __all__ = ['poly_mmd_sums', 'is_scores']
 
-P, I, F = nat.c_void_p, nat.c_int, nat.c_f64
-nat.register("diagan_poly_mmd_ws", [I])
-nat.register("diagan_poly_mmd_sums", [P, I, I, I, P, I, I, I, P, P, I, I, I, I, F, F, P, P, P])
-nat.register("diagan_is_ws", [I, I, I])
-nat.register("diagan_is_scores", [P, I, I, I, I, P, P, P])
-
 
 def _features(t, what):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and t.dtype in (torch.float32, torch.float64) and t.stride(1) == 1):

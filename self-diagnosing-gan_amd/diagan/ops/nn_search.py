@@ -5,24 +5,15 @@ Nq x Nc matrix is stored.  Ties go to the lowest index, however the candidates w
 
 torch only allocates memory here; every number is computed by the library.  Inputs are finite fp32 device tensors [N, D] with unit
 column stride (rows may have a stride)."""
-import ctypes
-
 import torch
 
 from diagan import _native as nat
 
 __all__ = ['nearest_rows', 'NearestSearch']
 
-P, I, L = nat.c_void_p, nat.c_int, nat.c_i64
-nat.register("diagan_nn_argmin", [P, I, I, P, I, I, P, I, L, I, P, P, P, P])
-nat.register("diagan_nn_argmin_ws", [I, I])
-nat.register("diagan_row_sqnorm", [P, P, I, I, I, P])      # (shared with trainer/compute_pr.py: the same signature)
-
 
 def _ws_bytes(Nq, Nc):
-    f = nat.fn("diagan_nn_argmin_ws")
-    f.restype = ctypes.c_size_t
-    return int(f(Nq, Nc))
+    return nat.fn("diagan_nn_argmin_ws")(Nq, Nc)
 
 
 def _check(name, t):

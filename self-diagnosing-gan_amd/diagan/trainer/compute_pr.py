@@ -13,12 +13,6 @@ from diagan.ops import conv as C
 
 __all__ = ['compute_pr']
 
-P, I = nat.c_void_p, nat.c_int
-nat.register("diagan_row_sqnorm", [P, P, I, I, I, P])
-nat.register("diagan_kth_smallest_rows", [P, P, I, I, I, I, P, P])
-nat.register("diagan_any_lt_rows", [P, P, P, P, I, I, I, P, P])
-nat.register("diagan_any_lt_cols", [P, P, P, P, I, I, I, P, P])
-
 _ROW_BLOCK = 8192
 
 

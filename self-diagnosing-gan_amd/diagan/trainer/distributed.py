@@ -36,23 +36,13 @@ def comm_description():
     return f"torch.distributed/{dist.get_backend()} ({_NATIVE['why']})"
 
 
-def _register_native():
-    from diagan import _native as nat
-    P, I, I64 = nat.c_void_p, nat.c_int, nat.c_i64
-    for name, sig in (("diagan_comm_unique_id", [P]), ("diagan_ctx_create", [P, P, I, I, I]), ("diagan_ctx_destroy", [P]),
-                      ("diagan_ctx_rank", [P]), ("diagan_ctx_world", [P]), ("diagan_allreduce_grads", [P, P, I64, P]),
-                      ("diagan_allgather_logits", [P, P, P, I64, I, P])):
-        nat.register(name, sig)
-    return nat
-
-
 def init_native_comm(rank, world, device_index):
     """Create the process's diagan_ctx: rank 0 draws the unique id, every rank receives it (torch.distributed object
     broadcast when a process group exists, else world must be 1), all ranks enter ncclCommInitRank together.
     The context is destroyed at interpreter exit (`destroy_native_comm`, atexit)."""
     import atexit
     import ctypes
-    nat = _register_native()
+    from diagan import _native as nat
     ident = ctypes.create_string_buffer(128)
     id_err = None
     if rank == 0:
@@ -80,7 +70,7 @@ def init_native_comm(rank, world, device_index):
 
 def destroy_native_comm():
     if _NATIVE['ctx'] is not None:
-        nat = _register_native()
+        from diagan import _native as nat
         if torch.cuda.is_available():
             torch.cuda.synchronize()        # nothing of ours may still be queued on the communicator
         nat.call("diagan_ctx_destroy", _NATIVE['ctx'])

@@ -172,10 +172,9 @@ def test_injected_zoom_is_bounded():
 def test_header_names_library_and_registered_signatures():
     import ctypes
     from diagan import _native as nat
-    import diagan.ops  # noqa: F401
     declared = set(_declared())
     assert AUG_ENTRY_POINTS <= declared, AUG_ENTRY_POINTS - declared
-    assert AUG_ENTRY_POINTS <= set(nat._SIGS), AUG_ENTRY_POINTS - set(nat._SIGS)
+    assert AUG_ENTRY_POINTS <= set(nat.signatures()), AUG_ENTRY_POINTS - set(nat.signatures())
     L = ctypes.CDLL(nat.LIB_PATH)
     assert all(hasattr(L, n) for n in AUG_ENTRY_POINTS)
     from diagan.models.op import augment as A
@@ -185,7 +184,6 @@ def test_header_names_library_and_registered_signatures():
 def test_workspace_query_and_its_checks():
     import ctypes
     from diagan import _native as nat
-    import diagan.ops  # noqa: F401
     b = ctypes.c_int64(0)
     nat.call("diagan_augment_workspace", 2, 16, 16, 0, 0, 0, 0, 0, ctypes.byref(b))
     h2 = 2 * (16 + 12) - 11

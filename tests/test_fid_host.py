@@ -58,10 +58,9 @@ def test_statistics_npz_round_trip(tmp_path):
 
 def test_header_names_equal_registered_signatures_after_importing_ops():
     from diagan import _native as nat
-    import diagan.ops  # noqa: F401
     declared = set(_declared())
     assert FID_ENTRY_POINTS <= declared, FID_ENTRY_POINTS - declared
-    assert FID_ENTRY_POINTS <= set(nat._SIGS), FID_ENTRY_POINTS - set(nat._SIGS)
+    assert FID_ENTRY_POINTS <= set(nat.signatures()), FID_ENTRY_POINTS - set(nat.signatures())
 
 
 def test_newton_schulz_rule_constants():

@@ -1,6 +1,8 @@
-"""CPU: libdiagan_hip.so loads and exports every symbol include/diagan_hip.h declares.
-No compute calls (no GPU here)."""
+"""CPU: libdiagan_hip.so loads and exports every symbol include/diagan_hip.h declares, and the ctypes signatures read from that
+header are the ones the package used to keep by hand.  No compute calls (no GPU here)."""
+import ast
 import ctypes
+import json
 import os
 import re
 
@@ -30,14 +32,138 @@ def test_library_loads_and_exports_all_symbols():
     assert nat.fn("diagan_abi_version")() >= 1
 
 
-def test_binding_table_matches_header():
+def test_signatures_from_the_header_equal_the_hand_written_table():
+    """tests/golden/abi_signatures.json is the table the op modules kept by hand (tools/abi_signatures.py on the last commit that had
+    it; every result bound as c_int).  The table read from the header has the same names and the same argument types, and the same
+    result type except for the three entry points whose results the header declares wider than an int."""
     from diagan import _native as nat
-    import diagan.ops  # noqa: F401  (registers the op signatures)
-    import diagan.trainer.compute_pr  # noqa: F401  (registers the precision/recall entry points)
-    from diagan.trainer import distributed as D
-    D._register_native()                 # the RCCL context entry points (csrc/comm.hip)
-    declared = set(_declared()) - {"diagan_last_error", "diagan_target_arch"}
-    assert declared == set(nat._SIGS), declared ^ set(nat._SIGS)
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_signatures.json")))
+    sigs = dict(nat.signatures())
+    for name in ("diagan_last_error", "diagan_target_arch"):
+        assert sigs.pop(name) == (ctypes.c_char_p, [])
+    assert len(golden) == 156 and set(sigs) == set(golden), set(sigs) ^ set(golden)
+    assert set(sigs) | {"diagan_last_error", "diagan_target_arch"} == set(_declared())
+    wide = {"diagan_wino_weight_blocks": ctypes.c_int64, "diagan_colred_workspace": ctypes.c_int64,
+            "diagan_nn_argmin_ws": ctypes.c_size_t}
+    for name, (restype, argtypes) in sigs.items():
+        assert [t.__name__ for t in argtypes] == golden[name]["argtypes"], name
+        if name in wide:
+            assert restype is wide[name] and golden[name]["restype"] == "c_int", name
+        else:
+            assert restype.__name__ == golden[name]["restype"] == "c_int", name
+
+
+def _entry_point_names(path):
+    """The string literals in the first argument of every nat.fn(...) / nat.call(...) of a source file; (path, line) of the calls
+    that pass a computed name instead."""
+    names, computed = set(), []
+    for node in ast.walk(ast.parse(open(path).read(), path)):
+        if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in ("fn", "call")
+                and isinstance(node.func.value, ast.Name) and node.func.value.id == "nat" and node.args):
+            lits = {c.value for c in ast.walk(node.args[0]) if isinstance(c, ast.Constant) and isinstance(c.value, str)}
+            names |= lits
+            if not lits:
+                computed.append((os.path.relpath(path, ROOT), ast.unparse(node.args[0])))
+    return names, computed
+
+
+def test_every_entry_point_named_at_a_call_site_is_declared():
+    """The table is the header, so a name the header lacks fails at its first call -- on the GPU.  Every name the package, the tools and
+    the tests hand to nat.fn / nat.call is declared; the two call sites that compute the name are enumerated."""
+    declared = set(_declared())
+    names, computed = set(), []
+    for top in (os.path.join(ROOT, "self-diagnosing-gan_amd"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
+        for d, _, files in os.walk(top):
+            for f in files:
+                if f.endswith(".py"):
+                    n, c = _entry_point_names(os.path.join(d, f))
+                    names |= n
+                    computed += c
+    assert len(names) > 100 and not names - declared, sorted(names - declared)
+    assert sorted(computed) == [("self-diagnosing-gan_amd/diagan/models/op/augment.py", "name"),
+                                ("self-diagnosing-gan_amd/diagan/utils/plot.py", "fn_name")], computed
+    # ... whose values are: augment._launch's two callers, and calculate_scores' exact / fp32 scorer
+    assert {"diagan_augment_forward", "diagan_augment_backward", "diagan_ldr_scores_f64", "diagan_ldr_scores_f32"} <= declared
+    src = open(os.path.join(ROOT, "self-diagnosing-gan_amd", "diagan", "models", "op", "augment.py")).read()
+    assert set(re.findall(r'_launch\("(\w+)"', src)) == {"diagan_augment_forward", "diagan_augment_backward"}
+    src = open(os.path.join(ROOT, "self-diagnosing-gan_amd", "diagan", "utils", "plot.py")).read()
+    assert set(re.findall(r'fn_name, ws_elt = [\w.]+, "(\w+)"', src)) == {"diagan_ldr_scores_f64", "diagan_ldr_scores_f32"}
+
+
+def test_no_module_has_to_be_imported_for_an_entry_point():
+    import subprocess
+    import sys
+    code = (f"import sys; sys.path.insert(0, {os.path.join(ROOT, 'self-diagnosing-gan_amd')!r})\n"
+            "from diagan import _native as nat\n"
+            "assert nat._sigs is None                      # the header is not read at import\n"
+            "assert nat.fn('diagan_conv_gemm_tile_rows')(11) == 256 and nat.fn('diagan_is_ws')(10, 1008, 10) == 10100\n"
+            "assert not [m for m in sys.modules if m.startswith('diagan.') and m != 'diagan._native']\n")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-800:]
+
+
+SYNTHETIC = """
+/* a block comment with diagan_x(int) in it; and (parentheses) */
+#define DIAGAN_OK 0
+#ifdef __cplusplus
+extern "C" {
+#endif
+const char* diagan_text(void);   // a line comment with diagan_y( in it
+int diagan_none();
+typedef struct diagan_opts {
+  int32_t a, b;
+  float* slab[2];   /* [splits][stride] */
+} diagan_opts;
+typedef struct diagan_ctx diagan_ctx;
+int diagan_many(const float* x, int B, float s, double d,
+                int64_t n, long off,
+                unsigned long long* stamps, void* stream);
+int64_t diagan_wide(int64_t M, int C);
+size_t diagan_bytes(int, int);
+int diagan_ctx_make(diagan_ctx** out, const diagan_opts* opts, const diagan_ctx *ctx, const void* id, long* idx, int * h);
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_parser_on_synthetic_header_text():
+    from diagan import _native as nat
+    V, I, F, D, L, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_long, ctypes.c_int64
+    assert nat.parse_header(SYNTHETIC) == {
+        "diagan_text": (ctypes.c_char_p, []),
+        "diagan_none": (I, []),
+        "diagan_many": (I, [V, I, F, D, I64, L, V, V]),
+        "diagan_wide": (I64, [I64, I]),
+        "diagan_bytes": (ctypes.c_size_t, [I, I]),
+        "diagan_ctx_make": (I, [V, V, V, V, V, V]),
+    }
+
+
+@pytest.mark.parametrize("decl", [
+    "int diagan_bad(short x);",                        # a parameter type outside the table
+    "int diagan_bad(int a, unsigned n);",
+    "int diagan_bad(float x[4]);",                     # an array
+    "int diagan_bad(struct opts o);",                  # a struct by value
+    "unsigned diagan_bad(int a);",                     # a return type outside the table
+    "float* diagan_bad(void);",
+    "void diagan_bad(int a);",
+    "int diagan_bad(int (*cb)(int));",                 # a function pointer
+    "static inline int diagan_bad(int a) { return a; }",
+    "#define API\nAPI int diagan_bad(int a);",        # a macro in a prototype
+])
+def test_parser_names_the_declaration_it_cannot_bind(decl):
+    from diagan import _native as nat
+    with pytest.raises(ValueError, match="diagan_bad"):
+        nat.parse_header("int diagan_ok(int a);\n" + decl + "\nint diagan_after(void);\n")
+
+
+def test_missing_header_fails_loudly(monkeypatch):
+    from diagan import _native as nat
+    monkeypatch.setattr(nat, "_sigs", None)
+    monkeypatch.setattr(nat, "HEADER_PATH", "/nonexistent/diagan_hip.h")
+    with pytest.raises(RuntimeError, match="diagan_hip.h not found"):
+        nat.signatures()
 
 
 def test_missing_library_fails_loudly(monkeypatch):
@@ -53,7 +179,6 @@ def test_launch_selection_queries_are_host_logic():
     qualifying 3x3 layer with enough workgroups, the nine-product convolution + average-pool launch and its data gradient
     for the down-sampling DBlocks' c2 (mimicry DBlock, predefined_models.py:38-40,76-78) -- checked here without a GPU."""
     from diagan import _native as nat
-    import diagan.ops  # noqa: F401
     pick = nat.fn("diagan_conv_gemm_pick_cfg_geom")
     pool, unpool = nat.fn("diagan_conv_wino_pool_supported"), nat.fn("diagan_conv_wino_unpool_supported")
     ws = 64 << 20
@@ -85,7 +210,6 @@ def test_grouped_prologue_never_gets_a_tile_that_straddles_two_groups():
     kernel's 256-row tile (--batch_size 50, n_dis 5: 6 groups of 3200 rows): the automatic choice must then be a kernel
     whose tile divides the group -- what diagan_conv_gemm itself launches -- instead of an error at launch time."""
     from diagan import _native as nat
-    import diagan.ops  # noqa: F401
     pick, grouped = nat.fn("diagan_conv_gemm_pick_cfg_geom"), nat.fn("diagan_conv_gemm_pick_cfg_grouped")
     rows = nat.fn("diagan_conv_gemm_tile_rows")
     ws = 64 << 20

@@ -53,7 +53,6 @@ CASES = [  # Co, Kp, splits per context, contexts, spectral norm, bias
 
 def test_finish_batched_against_float64():
     from diagan import _native as nat
-    from diagan.ops import conv  # noqa: F401  (registers the entry points)
     rng = np.random.default_rng(3)
     layers = [_layer(rng, *c) for c in CASES]
     dev = torch.device('cuda')
@@ -92,7 +91,6 @@ def test_finish_batched_against_float64():
 
 def test_finish_batched_is_deterministic():
     from diagan import _native as nat
-    from diagan.ops import conv  # noqa: F401
     rng = np.random.default_rng(4)
     d = _layer(rng, 64, 576, 12, 2, True, True)
     dev = torch.device('cuda')
