@@ -17,6 +17,7 @@ from pathlib import Path
 import torch
 from torch.utils import data
 
+from diagan.datasets.device import DeviceImages, DeviceLoader
 from diagan.datasets.predefined import get_predefined_dataset
 from diagan.datasets.sampler import ShardedSampler, make_weighted_sampler
 from diagan.models.predefined_models import get_gan_model
@@ -108,6 +109,13 @@ def make_loader(dataset, batch_size, num_workers=0, weights=None, floor=1e-6):
         sampler = ShardedSampler(sampler if sampler is not None else data.RandomSampler(dataset), dist.get_rank(), world)
     # pinned staging only with worker processes (the reference always runs 8 of them): in the main process every
     # batch would pay a synchronous host allocation (~2 ms per tensor, 40 ms per global step)
+    return _loader(dataset, batch_size, sampler, num_workers)
+
+
+def _loader(dataset, batch_size, sampler, num_workers):
+    """A device-resident dataset (datasets/device.py) is served by its own loader: same index stream, batches by one fetch launch."""
+    if isinstance(getattr(dataset, 'dataset', None), DeviceImages):
+        return DeviceLoader(dataset, batch_size, sampler=sampler)
     return data.DataLoader(dataset=dataset, batch_size=batch_size, shuffle=sampler is None, sampler=sampler,
                            num_workers=num_workers, pin_memory=num_workers > 0)
 
@@ -285,8 +293,7 @@ def _plain_weighted_loader(dataset, batch_size, num_workers, weights=None):
     world = dist.get_world_size()
     if world > 1:
         sampler = ShardedSampler(sampler if sampler is not None else data.RandomSampler(dataset), dist.get_rank(), world)
-    return data.DataLoader(dataset=dataset, batch_size=batch_size, shuffle=sampler is None, sampler=sampler,
-                           num_workers=num_workers, pin_memory=num_workers > 0)
+    return _loader(dataset, batch_size, sampler, num_workers)
 
 
 def color_mnist_phase1(argv=None, dataset=None):

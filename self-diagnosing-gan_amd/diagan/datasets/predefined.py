@@ -1,9 +1,11 @@
 """Dataset wrapper API of the reference (diagan-pkg/diagan/datasets/predefined.py:17-36).
 
 `WeightedDataset` is identical in behaviour: items are (data, target, weight, index).
-torchvision is not a dependency of the hot path, so `get_predefined_dataset` serves synthetic
-tensors of the real datasets' shapes ('cifar10' 32x32 N=50000, 'celeba' 64x64 N=162770,
-'color_mnist' 32x32 N=60000) unless a tensor dataset is supplied by the caller.
+`get_predefined_dataset` serves the real dataset, device-resident (datasets/device.py),
+when its files are found under `root` (datasets/readers.py; torchvision is not a dependency).
+Otherwise, unless a tensor dataset is supplied by the caller, it serves synthetic tensors of the
+real datasets' shapes ('cifar10' 32x32 N=50000, 'celeba' 64x64 N=162770, 'color_mnist' 32x32
+N=60000).
 """
 import numpy as np
 import torch
@@ -62,8 +64,32 @@ class SyntheticImages(Dataset):
         return self.data[lo:hi] if self.data is not None else None
 
 
+def load_device_dataset(dataset_name, root, num_data=None, device=None, **kwargs):
+    """The real dataset `dataset_name` from the files under `root`, transformed once (Resize + CenterCrop on the device) and kept
+    in HBM as uint8.  `num_data` builds the MNIST families (as in the reference); for cifar10 / celeba it keeps the first
+    `num_data` images (smoke runs)."""
+    from diagan.datasets import readers
+    from diagan.datasets.device import DeviceImages, to_device_images
+    from diagan.datasets.transform import IMG_SIZE
+    if dataset_name in ('color_mnist', 'mnist_fmnist'):
+        if num_data is not None:
+            kwargs['num_data'] = num_data
+        images, targets = readers.READERS[dataset_name](root, **kwargs)
+    else:
+        images, targets = readers.READERS[dataset_name](root, **kwargs)
+        if num_data is not None:
+            images, targets = images[:num_data], targets[:num_data]
+    return DeviceImages(to_device_images(images, IMG_SIZE[dataset_name], device), targets, name=dataset_name)
+
+
 def get_predefined_dataset(dataset_name, root=None, weights=None, num_data=None, dataset=None, **kwargs):
     if dataset is None:
+        from diagan.datasets import readers
+        if dataset_name in readers.READERS and readers.available(dataset_name, root, **kwargs):
+            dataset = load_device_dataset(dataset_name, root, num_data=num_data, **kwargs)
+            print(f'dataset {dataset_name}: {len(dataset)} images of {dataset.shape} from {root}, device-resident uint8')
+            return WeightedDataset(dataset=dataset, weights=weights)
+        print(f'dataset {dataset_name}: no files under {root}, serving synthetic images')
         n, c, h, w = DATASET_SHAPES[dataset_name]
         n = num_data if num_data is not None else n
         dataset = SyntheticImages(n, (c, h, w), materialize=n * c * h * w <= (1 << 28))
