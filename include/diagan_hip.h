@@ -399,7 +399,9 @@ int diagan_sn_power_iter(const float* W, float* u_buffer, float* sigma_buffer, f
                          float* v_out, float* state, float* work, int Co, int Kp, float eps,
                          int update_buffers, void* stream);
 
-/* All SN layers of one network in four launches.  table_dev: device array of n_layers descriptors. */
+/* All SN layers of one network in four launches.  table_dev: device array of n_layers descriptors.  The packers write only the
+ * live region of an operand (Wf: columns below RS*Ci, Wd: Ci rows of RS*Co columns); the padding columns keep what the caller put
+ * there, so the caller zeroes Wf and Wd once when it allocates them. */
 typedef struct {
   const float* W;    /* master weight [Co][Kp] */
   float* u_buf;      /* module buffer sn_u [Co] (updated iff update_buffers) */
