@@ -212,6 +212,7 @@ typedef struct diagan_conv_opts {
   int32_t wino, wino4, wino4x, gemm_x3, gemm_x3b, splitk_fused, force_ksplit, tune;
   int32_t* tickets;
   int64_t ticket_slots;
+  int32_t gemm_x3_resident;   /* the resident-image form of tile_cfg 16 (include/diagan_conv_x3.h): -1 default, 0, 1 */
 } diagan_conv_opts;
 int diagan_conv_gemm_next_opts(const diagan_conv_opts* opts);
 /* The options pending for the next diagan_conv_gemm call of the calling thread (every field at its default when none are), so that a

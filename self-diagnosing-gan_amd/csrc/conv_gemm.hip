@@ -36,8 +36,9 @@ extern "C" int diagan_conv_wino_supported(int Hi, int Wi, int Ci, int Ho, int Wo
                                           int off, int up);
 
 namespace diagan {
-int launch_gemm_x3(const ConvGemmArgs& a, float* ws, hipStream_t st);     // conv_gemm_x3.hip: bf16 pipe, exactly split operands
+int launch_gemm_x3(const ConvGemmArgs& a, float* ws, bool resident, hipStream_t st);     // conv_gemm_x3.hip: bf16 pipe, exactly split operands
 bool gemm_x3_geom_ok(const ConvGemmArgs& a);
+bool gemm_x3_resident_ok(const ConvGemmArgs& a);                          // ... its resident-image form (8 x 8 maps, Ci <= 128)
 long gemm_x3_ws_floats(int Co, int Kp);
 int launch_gemm_x3b(const ConvGemmArgs& a, const OutMap& map, float* ws, hipStream_t st);    // conv_gemm_x3b.hip: the same arithmetic on 128 x 128 tiles
 bool gemm_x3b_geom_ok(const ConvGemmArgs& a);
@@ -702,6 +703,12 @@ static int g_gemm_x3 = -1;                        // -1: DIAGAN_GEMM_X3 / defaul
 // default; 0 / 1: diagan_conv_gemm_set_x3b.  The automatic choice upgrades an implicit-GEMM pick (never a Winograd one) where the
 // launch has at least `x3b_min_tiles()` 128 x 128 tiles and four K-steps.
 static int g_gemm_x3b = -1;
+// the resident-image form of tile_cfg 16 (conv_gemm_x3.hip).  -1: DIAGAN_GEMM_X3_RESIDENT / default; 0 / 1: diagan_conv_gemm_set_x3_resident
+static int g_gemm_x3_resident = -1;
+// Its environment switch, defined here, once, and not in switches.h: that table is what tests/golden/conv_selection.json records row by
+// row, and this switch changes the answer of no selection query (tile_cfg, last_cfg and the kernel's label stay those of tile_cfg 16).
+// Default on: the 8 x 8 / Ci <= 128 launches keep their image in LDS across the nine taps (profiles/gemm_x3_resident.md)
+static Switch kGemmX3Resident{{"DIAGAN_GEMM_X3_RESIDENT", 1}};
 static int x3b_min_tiles() { return kGemmX3bMinTiles.env(); }
 // the output map of the NEXT diagan_conv_gemm call of this thread (diagan_conv_gemm_out_map); like the weights hint it holds for
 // exactly one call
@@ -716,15 +723,18 @@ struct CallOpts {
   int wino, wino4, wino4x, gemm_x3, gemm_x3b, splitk_fused, force_ksplit, tune;
   int* tickets;
   long ticket_slots;
+  int gemm_x3_resident;
 };
-static const CallOpts kNoOpts = {-1, -1, -1, -1, -1, -1, 0, -1, nullptr, 0};
+static const CallOpts kNoOpts = {-1, -1, -1, -1, -1, -1, 0, -1, nullptr, 0, -1};
 static thread_local CallOpts g_opts_next = kNoOpts, g_opts_now = kNoOpts;
 static thread_local int g_last_cfg = 0;           // tile configuration the last call of this thread resolved to
+static thread_local int g_last_x3_form = 0;       // form its last tile_cfg 16 launch ran: 1 per-tap, 2 resident image (0: none yet)
 int call_opt_wino4x() { return g_opts_now.wino4x; }          // (conv_wino4.hip: wino4_get_x3)
 static int sel_wino() { return kWino.get(g_opts_now.wino, g_wino); }
 static int sel_wino4() { return g_opts_now.wino4 >= 0 ? g_opts_now.wino4 : g_wino4; }      // (-1: the environment's DIAGAN_WINO4 decides, at its use)
 static int sel_force_ksplit() { return g_opts_now.force_ksplit > 0 ? g_opts_now.force_ksplit : g_force_ksplit; }
 static bool gemm_x3_on() { return kGemmX3.get(g_opts_now.gemm_x3, g_gemm_x3) != 0; }
+static bool gemm_x3_resident_on() { return kGemmX3Resident.get(g_opts_now.gemm_x3_resident, g_gemm_x3_resident) != 0; }
 static bool gemm_x3b_on() { return kGemmX3b.get(g_opts_now.gemm_x3b, g_gemm_x3b) != 0; }
 static bool x3b_takes(const ConvGemmArgs& a, int cfg, int64_t ws_floats) {
   if (!gemm_x3b_on() || !(cfg == 1 || cfg == 3 || cfg == 5 || cfg == 7 || cfg == 8)) return false;
@@ -1083,7 +1093,9 @@ DIAGAN_API int diagan_conv_gemm(const float* x, const float* w, float* y, const 
                "32-channel K-steps, Kp == R*S*Ci, prologue none / ReLU, no statistics, and %ld floats of workspace", gemm_x3_ws_floats(Co, Kp));
     a.ksplit = 1;
     g_last_cfg = 16;                        // (the upgrade of a lone-tile pick: report the kernel that runs, as final_cfg does)
-    return launch_gemm_x3(a, splitk_ws, st);
+    const bool resident = gemm_x3_resident_on() && gemm_x3_resident_ok(a);
+    g_last_x3_form = resident ? 2 : 1;
+    return launch_gemm_x3(a, splitk_ws, resident, st);
   }
   if (cfg == 17) {
     DG_REQUIRE(gemm_x3b_geom_ok(a) && splitk_ws && gemm_x3b_ws_floats(Co, Kp) <= splitk_ws_floats,
@@ -1243,6 +1255,22 @@ DIAGAN_API int diagan_conv_gemm_set_x3b(int mode) {
   return DIAGAN_OK;
 }
 DIAGAN_API int diagan_conv_gemm_get_x3b(void) { return gemm_x3b_on() ? 1 : 0; }
+// ---- include/diagan_conv_x3.h: the resident-image form of tile_cfg 16 ----
+DIAGAN_API int diagan_conv_gemm_set_x3_resident(int mode) {
+  DG_REQUIRE(mode >= -1 && mode <= 1, "set_x3_resident: -1, 0 or 1");
+  g_gemm_x3_resident = mode;
+  return DIAGAN_OK;
+}
+DIAGAN_API int diagan_conv_gemm_get_x3_resident(void) { return gemm_x3_resident_on() ? 1 : 0; }
+DIAGAN_API int diagan_conv_gemm_last_x3_form(void) { return g_last_x3_form; }
+DIAGAN_API int diagan_conv_gemm_x3_resident_ok(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr, int off,
+                                               int up, int Kp, int pro_mode) {
+  ConvGemmArgs a = {};
+  a.pro_mode = pro_mode;
+  a.M = B * Ho * Wo;
+  a.g = ConvGeom{B, Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up, R * S * Ci, Kp};
+  return gemm_x3_resident_ok(a) ? 1 : 0;
+}
 namespace diagan { void x3_set_pieces(int n); int x3_pieces(); }
 // see include/diagan_hip.h: pieces per operand of the large split-operand kernels (process-level diagnostic / opt-in switch)
 DIAGAN_API int diagan_conv_gemm_set_x3_pieces(int n) {
@@ -1301,12 +1329,13 @@ DIAGAN_API int diagan_conv_gemm_set_splitk_tickets(int* buf, int64_t slots) {
   g_ticket_slots = (long)slots;
   return DIAGAN_OK;
 }
-struct diagan_conv_opts {     // mirrors the typedef of the same name in include/diagan_hip.h (48 bytes)
+struct diagan_conv_opts {     // mirrors the typedef of the same name in include/diagan_hip.h (56 bytes)
   int32_t wino, wino4, wino4x, gemm_x3, gemm_x3b, splitk_fused, force_ksplit, tune;
   int32_t* tickets;
   int64_t ticket_slots;
+  int32_t gemm_x3_resident;
 };
-static_assert(sizeof(diagan_conv_opts) == 48, "diagan_conv_opts layout");
+static_assert(sizeof(diagan_conv_opts) == 56, "diagan_conv_opts layout");
 // Selection options of the NEXT diagan_conv_gemm call of the calling thread (thread-local, consumed by that call whatever path it takes;
 // NULL clears a pending set).  See diagan_conv_opts in include/diagan_hip.h.
 DIAGAN_API int diagan_conv_gemm_next_opts(const diagan_conv_opts* o) {
@@ -1316,11 +1345,11 @@ DIAGAN_API int diagan_conv_gemm_next_opts(const diagan_conv_opts* o) {
   }
   DG_REQUIRE(o->wino >= -1 && o->wino <= 1 && o->wino4 >= -1 && o->wino4 <= 2 && o->wino4x >= -1 && o->wino4x <= 1 && o->gemm_x3 >= -1 &&
                  o->gemm_x3 <= 1 && o->gemm_x3b >= -1 && o->gemm_x3b <= 1 && o->splitk_fused >= -1 && o->splitk_fused <= 1 &&
-                 o->force_ksplit >= 0 && o->tune >= -1,
+                 o->force_ksplit >= 0 && o->tune >= -1 && o->gemm_x3_resident >= -1 && o->gemm_x3_resident <= 1,
              "conv_gemm_next_opts: a field out of range (-1 = process default; force_ksplit 0 = the launch policy)");
   DG_REQUIRE(!o->tickets || o->ticket_slots > 0, "conv_gemm_next_opts: a ticket buffer needs its slot count");
   g_opts_next = CallOpts{o->wino, o->wino4, o->wino4x, o->gemm_x3, o->gemm_x3b, o->splitk_fused, o->force_ksplit, o->tune, o->tickets,
-                         (long)o->ticket_slots};
+                         (long)o->ticket_slots, o->gemm_x3_resident};
   return DIAGAN_OK;
 }
 // the options pending for the next diagan_conv_gemm call of the calling thread (all defaults when none are): a caller that adds a field
@@ -1329,7 +1358,7 @@ DIAGAN_API int diagan_conv_gemm_pending_opts(diagan_conv_opts* o) {
   DG_REQUIRE(o, "conv_gemm_pending_opts: null");
   const CallOpts& c = g_opts_next;
   *o = diagan_conv_opts{c.wino, c.wino4, c.wino4x, c.gemm_x3, c.gemm_x3b, c.splitk_fused, c.force_ksplit, c.tune, c.tickets,
-                        (int64_t)c.ticket_slots};
+                        (int64_t)c.ticket_slots, c.gemm_x3_resident};
   return DIAGAN_OK;
 }
 // tile configuration the last diagan_conv_gemm call of the calling thread resolved to (0: it failed before choosing)

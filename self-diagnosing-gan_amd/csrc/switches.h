@@ -1,5 +1,5 @@
-// The kernel-selection switches of libdiagan_hip.so: every DIAGAN_* environment variable the host code reads, defined once with its
-// default.  INTEGRATION.md section 2 lists them in this order.
+// The kernel-selection switches of libdiagan_hip.so: every DIAGAN_* environment variable the host code reads for a selection query,
+// defined once with its default.  INTEGRATION.md section 2 lists them in this order.
 #pragma once
 #include <atomic>
 #include <stdlib.h>
@@ -61,6 +61,8 @@ inline Switch kKg2{{"DIAGAN_KG2", 1}};                           // 0: no two-K-
 inline Switch kKsplit{{"DIAGAN_KSPLIT", 0}};                     // tuning experiments only: forced split-K factor
 inline Switch kSplitkFused{{"DIAGAN_SPLITK_FUSED", 0}};          // in-kernel split-K combine: off, it buys nothing (see splitk_tickets)
 inline Switch kGemmX3{{"DIAGAN_GEMM_X3", 1}};                    // on: SNGAN-32 5270-5281 -> 5355 images/s
+// (DIAGAN_GEMM_X3_RESIDENT, the form of the tile_cfg 16 kernel, selects no tile configuration and changes no selection query's answer:
+//  it is defined in conv_gemm.hip beside its setter, outside the table the selection fixture tests/golden/conv_selection.json goes by)
 inline Switch kGemmX3b{{"DIAGAN_GEMM_X3B", 1}};
 inline Switch kGemmX3bMinTiles{{"DIAGAN_GEMM_X3B_MIN_TILES", 192}};
 inline Switch kX3Pieces{{"DIAGAN_X3_PIECES", 3}};                // pieces per operand of the large split-operand kernels: 3, or 2 (opt-in)

@@ -243,6 +243,33 @@ def set_gemm_x3(on):
     nat.call("diagan_conv_gemm_set_x3b", -1 if on is None else (1 if on else 0))
 
 
+def set_gemm_x3_resident(on):
+    """True / False: the tile_cfg 16 launches whose tile is one whole 8 x 8 image (3x3 / pad 1, Ci <= 128) keep that image in LDS across
+    the nine taps / stage it per tap (csrc/conv_gemm_x3.hip; bit-identical results); None: what DIAGAN_GEMM_X3_RESIDENT says"""
+    from diagan._native import conv_x3_abi as xnat
+    xnat.call("diagan_conv_gemm_set_x3_resident", -1 if on is None else (1 if on else 0))
+
+
+def last_x3_form():
+    """form the last tile_cfg 16 launch of this thread ran: 1 per-tap, 2 resident image (0: none yet)"""
+    from diagan._native import conv_x3_abi as xnat
+    return xnat.fn("diagan_conv_gemm_last_x3_form")()
+
+
+def gemm_x3_resident_ok(geom, B, Hi, Wi, dgrad=False, mode=PRO_NONE):
+    """whether a tile_cfg 16 launch of this layer's forward (its data gradient: dgrad, Hi x Wi = dy's size) qualifies for the
+    resident-image form"""
+    from diagan._native import conv_x3_abi as xnat
+    if dgrad:
+        sy, dr, off, up = geom.dgrad_params()
+        return bool(xnat.fn("diagan_conv_gemm_x3_resident_ok")(B, Hi, Wi, geom.Co, Hi, Wi, geom.Ci, geom.R, geom.S, sy, dr, off, up,
+                                                               geom.Kd, mode))
+    sy, dr, off, up = geom.fwd_params()
+    Ho, Wo = geom.out_hw(Hi, Wi)
+    return bool(xnat.fn("diagan_conv_gemm_x3_resident_ok")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up,
+                                                           geom.Kp, mode))
+
+
 def set_gemm_x3b(on):
     """the same for the 128 x 128 / 256 x 128 split-operand kernel alone (tile_cfg 17); None: what DIAGAN_GEMM_X3B says"""
     nat.call("diagan_conv_gemm_set_x3b", -1 if on is None else (1 if on else 0))
@@ -287,13 +314,14 @@ class ConvOpts(_ct.Structure):
     """diagan_conv_opts (include/diagan_hip.h): the selection options of ONE call -- `with conv_opts(wino=0): conv_fwd(...)` hands them
     to the next diagan_conv_gemm call of this thread; nothing process-wide is touched"""
     _fields_ = [(n, _ct.c_int32) for n in ("wino", "wino4", "wino4x", "gemm_x3", "gemm_x3b", "splitk_fused", "force_ksplit", "tune")] + \
-               [("tickets", _ct.c_void_p), ("ticket_slots", _ct.c_int64)]
+               [("tickets", _ct.c_void_p), ("ticket_slots", _ct.c_int64), ("gemm_x3_resident", _ct.c_int32)]
 
 
 def next_opts(tickets=None, **fields):
-    """options of the next convolution launch of this thread: wino / wino4 / wino4x / gemm_x3 / gemm_x3b / splitk_fused (-1 default, 0, 1),
-    force_ksplit (0 = policy), tune (-1 default); tickets: a zeroed int32 CUDA tensor for the in-kernel split-K combine"""
-    o = ConvOpts(-1, -1, -1, -1, -1, -1, 0, -1, None, 0)
+    """options of the next convolution launch of this thread: wino / wino4 / wino4x / gemm_x3 / gemm_x3b / splitk_fused /
+    gemm_x3_resident (-1 default, 0, 1), force_ksplit (0 = policy), tune (-1 default); tickets: a zeroed int32 CUDA tensor for the
+    in-kernel split-K combine"""
+    o = ConvOpts(-1, -1, -1, -1, -1, -1, 0, -1, None, 0, -1)
     for k, v in fields.items():
         setattr(o, k, int(v))
     if tickets is not None:
@@ -309,7 +337,7 @@ def pending_opts():
 
 
 def _opts_key(o):
-    return tuple(getattr(o, n) for n, _ in ConvOpts._fields_[:8])
+    return tuple(getattr(o, n) for n, _ in ConvOpts._fields_[:8]) + (o.gemm_x3_resident,)
 
 
 def _without_wino(o):

@@ -53,7 +53,7 @@ OPT_FIELDS = ("wino", "wino4", "wino4x", "gemm_x3", "gemm_x3b", "splitk_fused", 
 
 
 class ConvOpts(ctypes.Structure):      # diagan_conv_opts, include/diagan_hip.h
-    _fields_ = [(n, ctypes.c_int32) for n in OPT_FIELDS] + [("tickets", P), ("ticket_slots", L)]
+    _fields_ = [(n, ctypes.c_int32) for n in OPT_FIELDS] + [("tickets", P), ("ticket_slots", L), ("gemm_x3_resident", ctypes.c_int32)]
 
 
 def _fwd(B, H, W, Ci, Co, k=3, stride=1, pad=1, group=0):
@@ -166,7 +166,7 @@ def table(fn, labels=False):
 def run_here(fn, name):
     """answers under the set: / opt: steps of a setting, which are put back afterwards (its env: steps are the caller's business)"""
     steps = [s.split(":", 1) for s in name.split("+")] if name != "defaults" else []
-    opts, done = ConvOpts(-1, -1, -1, -1, -1, -1, 0, -1, None, 0), []
+    opts, done = ConvOpts(-1, -1, -1, -1, -1, -1, 0, -1, None, 0, -1), []
     try:
         for kind, body in steps:
             key, val = body.split("=", 1)
