@@ -1,0 +1,12 @@
+#!/usr/bin/env python
+"""FID against the real samples of highest and lowest phase-1 weight on the MI355X engine (the reference's script of this name): see
+diagan/eval_cli.py."""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "self-diagnosing-gan_amd"))
+
+from diagan.eval_cli import eval_gan_with_index as main, eval_with_index_parser as build_parser  # noqa: E402,F401
+
+if __name__ == '__main__':
+    main()
