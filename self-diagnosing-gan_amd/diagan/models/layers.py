@@ -586,18 +586,41 @@ class SNBatch:
                 m._slot_ctx[slot].wver = self.slot_ver[slot]
 
 
+class WgradEntry:
+    """One layer's split-K slab in one context slot of a WgradBatch: [splits][stride] partials of the weight gradient (n_w
+    elements) and, behind them at bias_off, of the bias gradient (-1: none); n_elem == stride of them are reduced.  own_splits is
+    the count of the layer's own chip-filling launch, splits the count the slab has now (a batched launch gives it another);
+    partials: the float64 scratch of the finish kernels; sn_ctx: the spectral-norm context(s) of the pass that wrote the slab."""
+    __slots__ = ("owner", "slot", "M", "n_w", "n_elem", "stride", "splits", "own_splits", "bias_off", "segments", "slab",
+                 "partials", "sn_ctx")
+
+    def __init__(self, owner, slot, M, n_w, stride, splits, bias_off, segments, dev):
+        self.owner, self.slot, self.M, self.n_w, self.n_elem, self.stride = owner, slot, M, n_w, stride, stride
+        self.splits, self.own_splits, self.bias_off, self.segments, self.sn_ctx = splits, splits, bias_off, segments, None
+        self.slab = torch.empty(splits * stride, dtype=torch.float32, device=dev)
+        self.partials = torch.empty((segments, (stride + 1023) // 1024 + 1), dtype=torch.float64, device=dev)   # (>= blocks of any size + 1)
+
+    def set_splits(self, splits):
+        """the slab takes another split count: a new slab, and the owner's finish tables of the slot, which hold the old one's
+        address and count, are dropped"""
+        if splits != self.splits:
+            self.splits = splits
+            self.slab = torch.empty(splits * self.stride, dtype=torch.float32, device=self.slab.device)
+            self.owner.drop_tables(self.slot)
+
+
 class WgradBatch:
-    QUEUE_BYTES = int(os.environ.get("DIAGAN_WGRAD_QUEUE_BYTES", str(8 << 30)))     # early-flush threshold of a slot's queue
     """Deferred weight-gradient epilogue of one network.
 
     Every parameterised GEMM layer owns one split-K slab per context slot; conv_wgrad_kernel writes its
     partials (weights and, fused, the bias column sums) there during the backward pass, and finish()
     reduces all layers in two launches (diagan_wgrad_finish_batched), including the spectral-norm
     correction.  Replaces 4-5 small launches per layer per pass."""
+    QUEUE_BYTES = int(os.environ.get("DIAGAN_WGRAD_QUEUE_BYTES", str(8 << 30)))     # early-flush threshold of a slot's queue
 
     def __init__(self, net):
         self.net = net
-        self.entries = {}        # (layer, slot) -> dict
+        self.entries = {}        # (layer, slot) -> WgradEntry
         self.launched = {}       # slot -> list of layers launched in the current pass
         self.tables = {}         # (slot, tuple(layer ids)) -> (table tensor, n, total_blocks, any_sn)
         self.slab_generation = None
@@ -607,25 +630,29 @@ class WgradBatch:
         self.hold = False
         self.pending = []
         self.overlapped = 0      # updates whose reduction was split (tests)
-        # Winograd weight gradients wait here until the end of the pass and then run as ONE launch per prologue mode
-        # (ops/conv.py: conv_wgrad_batched); the queue keeps dy and x alive.  Memory: every batchable layer's dy and x stay
+        # Batchable weight gradients wait here until the end of the pass and then run as ONE launch per kernel template
+        # (ops/conv.py: wgrad_launch_plan, conv_wgrad_batched); the queue keeps dy and x alive.  Memory: every batchable layer's dy and x stay
         # allocated until finish() instead of being freed as the backward pass moves on -- at most the activations + gradients
         # of one pass (SNGAN-64 at batch 64: ~1.3 GB, StyleGAN2 does not use this queue), bounded by QUEUE_BYTES below: a slot
         # whose queue passes it is flushed early (the layers so far launch as their own batch)
-        self.queue = {}          # slot -> [(layer, dy, x, pro, segments, entry)]
+        self.queue = {}          # slot -> [C.WgradJob]
         self.queued_bytes = {}   # slot -> bytes of dy + x the queue keeps alive
-        self.batch_plans = {}    # (layer ids, shapes) -> splits per layer
-        self.job_tables = {}     # (the same key, plan) -> constant columns of the batched launch's job table (ops/conv.py); lives and
-                                 # dies with this network, so the layer ids in its keys cannot be recycled under it
+        self.batch_plans = {}    # the queue's shapes -> its launches (C.wgrad_launch_plan)
+        self.job_tables = {}     # (the same key, launch number) -> constant columns of the batched launch's job table (ops/conv.py);
+                                 # both live and die with this network: the layers' Geom objects in their keys are not recycled
         self.batched_launches = 0
 
-    def _entry(self, layer, slot, M, segments=1, dy_shape=None, x_shape=None, geom=None):
+    def drop_tables(self, slot):
+        """forget the finish tables of `slot`: an entry of it has another slab"""
+        self.tables = {k: v for k, v in self.tables.items() if k[0] != slot}
+
+    def _entry(self, layer, slot, M, segments, dy_shape, x_shape, geom):
         self.net.flat_grads
         if self.slab_generation != self.net.slab_generation:          # gradient slab was re-allocated
             self.entries.clear(), self.tables.clear(), self.job_tables.clear()
             self.slab_generation = self.net.slab_generation
         e = self.entries.get((layer, slot))
-        if e is None or e['M'] != M:
+        if e is None or e.M != M:
             g = geom if geom is not None else layer.geom       # (an equivalent geometry with the same packed layout)
             n_w = g.Co * g.Kp
             has_bias = layer.bias is not None
@@ -633,20 +660,13 @@ class WgradBatch:
             if has_bias and layer.bias.grad.data_ptr() != layer.weight.grad.data_ptr() + 4 * n_w:
                 raise RuntimeError("bias gradient does not follow the weight gradient in the flat slab")
             stride = n_w + n_b
-            if dy_shape is not None and x_shape is not None:
-                base = C.wgrad_splits_geom(g, dy_shape[0], x_shape[1], x_shape[2], dy_shape[1], dy_shape[2])
-            else:
-                base = C.wgrad_splits(M, g.Co, g.Kp)
+            base = C.wgrad_splits_geom(g, dy_shape[0], x_shape[1], x_shape[2], dy_shape[1], dy_shape[2])
             splits = max(segments, base // segments * segments)
-            if segments == 1 and dy_shape is not None and C.small_co_wgrad(g):
+            if segments == 1 and C.small_co_wgrad(g):
                 splits = C.small_co_wgrad_splits(dy_shape[0], dy_shape[1])
-            dev = layer.weight.device
-            e = dict(M=M, n_w=n_w, n_elem=stride, stride=stride, splits=splits, own_splits=splits, bias_off=n_w if has_bias else -1,
-                     segments=segments,
-                     slab=torch.empty(splits * stride, dtype=torch.float32, device=dev),
-                     partials=torch.empty((segments, (stride + 1023) // 1024 + 1), dtype=torch.float64, device=dev))   # (>= blocks of any size + 1)
-            self.entries[(layer, slot)] = e
-            self.tables = {k: v for k, v in self.tables.items() if k[0] != slot}
+            e = self.entries[(layer, slot)] = WgradEntry(self, slot, M, n_w, stride, splits, n_w if has_bias else -1, segments,
+                                                         layer.weight.device)
+            self.drop_tables(slot)
         return e
 
     def launch(self, layer, slot, dy, x, pro, sn_ctx, segments=1, geom=None):
@@ -663,85 +683,43 @@ class WgradBatch:
             self._finish_layers(slot, self.launched.pop(slot, []))
         xs = C.wg_x_shape(x, pro)
         e = self._entry(layer, slot, M, segments, tuple(dy.shape), xs, geom)
-        e['sn_ctx'] = sn_ctx
+        e.sn_ctx = sn_ctx
         self.launched.setdefault(slot, []).append(layer)
+        g, pooled = (geom, True) if geom is not None else (layer.geom, False)
         if C.WGRAD_BATCH and dy.dim() == 4 and x.dim() == 4:
-            g = geom if geom is not None else layer.geom
-            cls = 0 if (segments == 1 and C.small_co_wgrad(g)) else C.wgrad_batch_class(
-                g, xs[1], xs[2], dy.shape[1], dy.shape[2], int(pro[0]) if pro is not None else 0)
-            if cls:
-                q = self.queue.setdefault(slot, [])
-                q.append((layer, dy, x, pro, segments, e, g, (cls, geom is not None)))
+            mode = int(pro[0]) if pro is not None else 0
+            if not (segments == 1 and C.small_co_wgrad(g)) and C.wgrad_batch_class(g, xs[1], xs[2], dy.shape[1], dy.shape[2], mode):
+                shape = C.WgradShape(g, tuple(dy.shape), tuple(xs), mode, segments, e.own_splits, pooled)
+                self.queue.setdefault(slot, []).append(C.WgradJob(layer, dy, x, pro, e, shape))
                 self.queued_bytes[slot] = self.queued_bytes.get(slot, 0) + 4 * (dy.numel() + x.numel())
                 if self.queued_bytes[slot] > self.QUEUE_BYTES:
                     self.flush(slot)
                 return
-        C.conv_wgrad_into(geom if geom is not None else layer.geom, dy, x, e['slab'], e['splits'], e['stride'], e['bias_off'],
-                          pro=pro, segments=segments, pooled=geom is not None)
+        C.conv_wgrad_into(g, dy, x, e.slab, e.splits, e.stride, e.bias_off, pro=pro, segments=segments, pooled=pooled)
 
     def flush(self, slot):
-        """launch the queued weight gradients of `slot`: one launch per kernel template (batch class; the pooled layers'
-        strided form apart, for the FLOP accounting) and per wgrad_batch_max() layers, every layer with the split count the
-        group's plan gives it; a group of one runs as an ordinary launch"""
+        """launch the queued weight gradients of `slot` as C.wgrad_launch_plan groups them (the plan is a function of the queue's
+        shapes, made once per distinct queue); every entry takes the split count the plan gives it"""
         jobs = self.queue.pop(slot, None)
         self.queued_bytes.pop(slot, None)
         if not jobs:
             return
-        groups = {}
-        for job in jobs:
-            groups.setdefault(job[7], []).append(job)
-        nmax = C.wgrad_batch_max()
-
-        def alone(job, pooled):
-            layer, dy, x, pro, segments, e, g, _ = job
-            if e['splits'] != e['own_splits']:       # (it ran in a batch before: back to its own chip-filling split count)
-                e['splits'] = e['own_splits']
-                e['slab'] = torch.empty(e['splits'] * e['stride'], dtype=torch.float32, device=dy.device)
-                self.tables = {k: v for k, v in self.tables.items() if k[0] != slot}
-            C.conv_wgrad_into(g, dy, x, e['slab'], e['splits'], e['stride'], e['bias_off'], pro=pro, segments=segments, pooled=pooled)
-
-        for (cls, pooled), grp in groups.items():
-            # (knob: a layer whose own chip-filling launch runs >= WGRAD_BATCH_MIN_STEPS K-steps per workgroup launches on its
-            #  own; default off -- ops/conv.py has the sweep: the generator's three big layers are 0.92 -> 1.03 ms slower
-            #  batched, and batching them still wins end to end through the slabs and launches it saves)
-            small = []
-            for job in grp:
-                layer, dy, x, pro, segments, e, g, _ = job
-                steps = C.wgrad_batch_shape(g, dy.shape[0], dy.shape[1], dy.shape[2], cls)[1]
-                if -(-steps // max(e['own_splits'], 1)) >= C.WGRAD_BATCH_MIN_STEPS:
-                    alone(job, pooled)
-                else:
-                    small.append(job)
-            grp = small
-            for lo in range(0, len(grp), nmax):
-                part = grp[lo: lo + nmax]
-                if len(part) == 1:
-                    alone(part[0], pooled)
-                    continue
-                key = (cls, pooled) + tuple((id(j[0]), tuple(j[1].shape), j[4]) for j in part)
-                plan = self.batch_plans.get(key)
-                if plan is None:
-                    desc, slots, fixed = [], 256, 8.0
-                    for layer, dy, x, pro, segments, e, g, _ in part:
-                        tiles, steps, slots, fixed = C.wgrad_batch_shape(g, dy.shape[0], dy.shape[1], dy.shape[2], cls)
-                        desc.append((tiles, steps, segments))
-                    plan = self.batch_plans[key] = C.batched_wgrad_splits(desc, slots, fixed)
-                for (layer, dy, x, pro, segments, e, g, _), sp in zip(part, plan):
-                    if e['splits'] != sp:                # the slab of this layer takes the batch's split count
-                        e['splits'] = sp
-                        e['slab'] = torch.empty(sp * e['stride'], dtype=torch.float32, device=dy.device)
-                        self.tables = {k: v for k, v in self.tables.items() if k[0] != slot}
-                name = None
-                if cls >= 1000:
-                    g0, d0 = part[0][6], part[0][1]
-                    name = C._wgrad_kernel_name(g0.Co, g0.Kp, int(part[0][3][0]) if part[0][3] is not None else 0, d0.shape[1],
-                                                d0.shape[2]).replace("conv_wgrad_kernel", "conv_wgrad_batched_kernel")
-                    if pooled:
-                        name += C.POOLED_TAG
-                C.conv_wgrad_batched([(g, dy, x, e['slab'], e['splits'], e['stride'], e['bias_off'], pro, segments)
-                                      for layer, dy, x, pro, segments, e, g, _ in part], key=(key, tuple(plan)),
-                                     kernel_name=name, flop_scale=4.0 if pooled else 1.0, cache=self.job_tables)
+        key = tuple(j.shape for j in jobs)
+        plan = self.batch_plans.get(key)
+        if plan is None:
+            plan = self.batch_plans[key] = C.wgrad_launch_plan(key)
+        for n, launch in enumerate(plan):
+            part = [jobs[j] for j in launch.jobs]
+            for job, splits in zip(part, launch.splits):
+                job.entry.set_splits(splits)
+            if len(part) > 1:
+                C.conv_wgrad_batched(part, launch.kernel_name, flop_scale=4.0 if launch.pooled else 1.0, key=(key, n),
+                                     cache=self.job_tables)
                 self.batched_launches += 1
+            else:
+                job, e = part[0], part[0].entry
+                C.conv_wgrad_into(job.shape.geom, job.dy, job.x, e.slab, e.splits, e.stride, e.bias_off, pro=job.pro,
+                                  segments=job.shape.segments, pooled=launch.pooled)
 
     def finish(self, slot):
         self.flush(slot)             # the partial sums are computed now, whatever happens to their reduction
@@ -760,7 +738,7 @@ class WgradBatch:
             return None
         base = self.net.flat_grads.data_ptr()
         lo = [(l.weight.grad.data_ptr() - base) // 4 for l in layers]
-        hi = [o + self.entries[(l, slot)]['n_elem'] for o, l in zip(lo, layers)]
+        hi = [o + self.entries[(l, slot)].n_elem for o, l in zip(lo, layers)]
         total, acc, best = sum(b - a for a, b in zip(lo, hi)), 0, None
         for h in range(1, len(layers)):            # late = layers[:h]: a valid cut leaves every early layer below it
             acc += hi[h - 1] - lo[h - 1]
@@ -787,27 +765,27 @@ class WgradBatch:
             any_sn, total_blocks = 0, 0
             for li, layer in enumerate(layers):
                 e = self.entries[(layer, slot)]
-                c = e['sn_ctx']
+                c = e.sn_ctx
                 ctxs = list(c) if isinstance(c, tuple) else [c]
                 nctx = len(ctxs)
-                per = e['splits'] // nctx                  # splits of each batched forward
+                per = e.splits // nctx                  # splits of each batched forward
                 sn = ctxs[0] is not None
                 any_sn |= int(sn)
                 pp = [0] * 12
                 for pi, cc in enumerate(ctxs):
-                    pp[0 + pi] = e['slab'].data_ptr() + 4 * pi * per * e['stride']
+                    pp[0 + pi] = e.slab.data_ptr() + 4 * pi * per * e.stride
                     if sn:
                         pp[2 + pi], pp[4 + pi], pp[6 + pi] = cc.u.data_ptr(), cc.v.data_ptr(), cc.state.data_ptr()
-                    pp[8 + pi] = e['partials'][pi].data_ptr()
+                    pp[8 + pi] = e.partials[pi].data_ptr()
                 if not sn and nctx > 1:                    # plain layer: one context over all splits
-                    nctx, per = 1, e['splits']
+                    nctx, per = 1, e.splits
                 pp[10] = layer.weight.grad.data_ptr()
                 pp[11] = layer.weight.data.data_ptr() if sn else 0
-                assert 64 * e['stride'] < 2 ** 31, "wgrad finish: 16 splits of a layer must fit a 2 GiB buffer window"
-                tab[li]['p'], tab[li]['stride'] = pp, e['stride']
-                tab[li]['i'] = [per, e['n_elem'], e['n_w'], layer.geom.Kp, nctx, total_blocks]
+                assert 64 * e.stride < 2 ** 31, "wgrad finish: 16 splits of a layer must fit a 2 GiB buffer window"
+                tab[li]['p'], tab[li]['stride'] = pp, e.stride
+                tab[li]['i'] = [per, e.n_elem, e.n_w, layer.geom.Kp, nctx, total_blocks]
                 be = nat.fn("diagan_wgrad_finish_block_elems")(per)          # elements per workgroup of the finish kernels
-                total_blocks += (e['n_elem'] + be - 1) // be
+                total_blocks += (e.n_elem + be - 1) // be
             t = (torch.from_numpy(tab.view(np.uint8).copy()).to(layers[0].weight.device), len(layers), total_blocks, any_sn)
             self.tables[key] = t
         nat.call("diagan_wgrad_finish_batched", t[0].data_ptr(), t[1], t[2], t[3], nat.current_stream())

@@ -99,6 +99,7 @@ _NAME_CACHE = {}
 # and transforms its own weights, and the site re-learns.  DIAGAN_WINO_BATCH=0: every launch transforms its own, as before.
 import ctypes as _ct
 import os as _os
+from collections import namedtuple as _namedtuple
 
 WINO_BATCH = _os.environ.get("DIAGAN_WINO_BATCH", "1") != "0"
 
@@ -225,6 +226,20 @@ class Geom:
     def dgrad_params(self):
         return (1, -1, self.pad, self.stride) if self.kind == 'conv' else (self.stride, 1, -self.pad, 1)
 
+    # The C ABI's geometry list (include/diagan_hip.h): B, Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up, Kp.  Every launch and host
+    # query of a layer takes it from one of these two; an entry point that takes a part of the list (no B, no Kp) slices the tuple.
+    def abi_fwd(self, B, Hi, Wi, out_hw=None):
+        """the list of the forward gather from an input [B,Hi,Wi,Ci] -- also the weight gradient's, which states its output size
+        (out_hw: dy's) and gathers from wg_x_shape's tensor"""
+        Ho, Wo = self.out_hw(Hi, Wi) if out_hw is None else out_hw
+        return (B, Hi, Wi, self.Ci, Ho, Wo, self.Co, self.R, self.S) + self.fwd_params() + (self.Kp,)
+
+    def abi_dgrad(self, B, Hi, Wi):
+        """the list of the data gradient of a layer whose input is [B,Hi,Wi,Ci]: the gathered tensor is the layer's OUTPUT, its
+        channels are the GEMM's K and the layer's inputs its columns"""
+        Ho, Wo = self.out_hw(Hi, Wi)
+        return (B, Ho, Wo, self.Co, Hi, Wi, self.Ci, self.R, self.S) + self.dgrad_params() + (self.Kd,)
+
 
 def _pro3(pro):
     """(mode, scale, shift) of a prologue tuple for the kernels that take ONE batch (weight gradients)."""
@@ -260,14 +275,10 @@ def gemm_x3_resident_ok(geom, B, Hi, Wi, dgrad=False, mode=PRO_NONE):
     """whether a tile_cfg 16 launch of this layer's forward (its data gradient: dgrad, Hi x Wi = dy's size) qualifies for the
     resident-image form"""
     from diagan._native import conv_x3_abi as xnat
-    if dgrad:
-        sy, dr, off, up = geom.dgrad_params()
-        return bool(xnat.fn("diagan_conv_gemm_x3_resident_ok")(B, Hi, Wi, geom.Co, Hi, Wi, geom.Ci, geom.R, geom.S, sy, dr, off, up,
-                                                               geom.Kd, mode))
-    sy, dr, off, up = geom.fwd_params()
-    Ho, Wo = geom.out_hw(Hi, Wi)
-    return bool(xnat.fn("diagan_conv_gemm_x3_resident_ok")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up,
-                                                           geom.Kp, mode))
+    # (dgrad: the 3x3 / stride 1 / pad 1 layers, the only ones the query says yes to, have dy's size for their input's too; for
+    #  every other layer its answer is no on the taps, sy, up and (dr, off) alone, whatever the sizes -- gemm_x3_halo.h)
+    geo = geom.abi_dgrad(B, Hi, Wi) if dgrad else geom.abi_fwd(B, Hi, Wi)
+    return bool(xnat.fn("diagan_conv_gemm_x3_resident_ok")(*geo, mode))
 
 
 def set_gemm_x3b(on):
@@ -288,9 +299,7 @@ def set_wgrad_x3(on):
 
 
 def wgrad_uses_x3(geom, B, Hi, Wi, Ho, Wo, mode=0, bias_off=-1):
-    sy, dr, off, up = geom.fwd_params()
-    return bool(nat.fn("diagan_conv_wgrad_uses_x3")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up, geom.Kp,
-                                                    mode, bias_off))
+    return bool(nat.fn("diagan_conv_wgrad_uses_x3")(*geom.abi_fwd(B, Hi, Wi, (Ho, Wo)), mode, bias_off))
 
 
 _TICKETS = {}
@@ -498,10 +507,8 @@ def res_up_fused(geom, B, Hi, Wi, want_stats=False, group_imgs=0):
     group_imgs: images per prologue group of the launch (0: ungrouped) -- part of the choice, see
     diagan_conv_gemm_pick_cfg_grouped."""
     Ho, Wo = geom.out_hw(Hi, Wi)
-    sy, dr, off, up = geom.fwd_params()
     ws = _splitk_ws(torch.device('cuda', torch.cuda.current_device()))
-    return nat.fn("diagan_conv_gemm_pick_cfg_grouped")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off,
-                                                       up, geom.Kp, 0 if want_stats else 1, ws.numel(),
+    return nat.fn("diagan_conv_gemm_pick_cfg_grouped")(*geom.abi_fwd(B, Hi, Wi), 0 if want_stats else 1, ws.numel(),
                                                        group_imgs * Ho * Wo) in (9, 13)
 
 
@@ -509,24 +516,18 @@ def upin_fused(geom, B, Hl, Wl, group_imgs=0):
     """Will conv_fwd(geom, x[B,Hl,Wl,Ci], ..., up_in=True) run?  True iff conv3x3(bilinear_x2(pro(x))) of this layer qualifies
     for the one-launch F(4x4) kernel on the half-resolution input (tile_cfg 15); otherwise the caller up-samples first
     (diagan_upsample2x).  group_imgs: images per prologue group (stacked generator forward), 0: ungrouped."""
-    Hi, Wi = 2 * Hl, 2 * Wl
-    Ho, Wo = geom.out_hw(Hi, Wi)
-    sy, dr, off, up = geom.fwd_params()
+    Ho, Wo = geom.out_hw(2 * Hl, 2 * Wl)
     ws = _splitk_ws(torch.device('cuda', torch.cuda.current_device()))
-    return bool(nat.fn("diagan_conv_wino4_upin_supported")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up,
-                                                           ws.numel(), group_imgs * Ho * Wo))
+    return bool(nat.fn("diagan_conv_wino4_upin_supported")(*geom.abi_fwd(B, 2 * Hl, 2 * Wl)[:13], ws.numel(), group_imgs * Ho * Wo))
 
 
 def pool_fused(geom, B, Hi, Wi, pro=None):
     """Will conv_fwd(geom, x[B,Hi,Wi,Ci], ..., pool=True) run?  True iff avg_pool2d(conv(pro(x)), 2) of this layer qualifies
     for the one-launch Winograd + pooling kernel (tile_cfg 11: 9 of the 16 transform-domain products) and the launch is
     large enough; otherwise the caller pools the convolution's output itself (diagan_avgpool2)."""
-    Ho, Wo = geom.out_hw(Hi, Wi)
-    sy, dr, off, up = geom.fwd_params()
     mode = pro[0] if pro is not None else PRO_NONE
     ws = _splitk_ws(torch.device('cuda', torch.cuda.current_device()))
-    return bool(nat.fn("diagan_conv_wino_pool_supported")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up,
-                                                          mode, ws.numel()))
+    return bool(nat.fn("diagan_conv_wino_pool_supported")(*geom.abi_fwd(B, Hi, Wi)[:13], mode, ws.numel()))
 
 
 def conv_fwd(geom, x, wf, bias=None, residual=None, pro=None, out=None, tile_cfg=0, res_relu=False, row_scale=None,
@@ -560,16 +561,13 @@ def out_map_ok(geom, B, Hi, Wi, pro=None, wino=True):
     """Will conv_fwd(geom, x[B,Hi,Wi,Ci], w, out=..., out_map=..., wino=wino) run?  True iff the automatic choice for this plain launch,
     under the options pending for it (next_opts) and with Winograd kept out where wino is False -- the launch's own inputs -- is the
     split-operand kernel (tile_cfg 17), the only one that writes through an output map."""
-    Ho, Wo = geom.out_hw(Hi, Wi)
-    sy, dr, off, up = geom.fwd_params()
     ws = _splitk_ws(torch.device('cuda', torch.cuda.current_device()))
     mode = pro[0] if pro is not None else PRO_NONE
     pend = None if wino else pending_opts()
     if pend is not None:
         nat.call("diagan_conv_gemm_next_opts", _ct.byref(_without_wino(pend)))
     try:
-        return nat.fn("diagan_conv_gemm_final_cfg")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up, geom.Kp, 1,
-                                                   ws.numel(), 0, mode, 1, 0) == 17
+        return nat.fn("diagan_conv_gemm_final_cfg")(*geom.abi_fwd(B, Hi, Wi), 1, ws.numel(), 0, mode, 1, 0) == 17
     finally:
         if pend is not None:
             nat.call("diagan_conv_gemm_next_opts", _ct.byref(pend))
@@ -602,23 +600,16 @@ def res_unpool_fused(geom, B, Hi, Wi):
     otherwise the caller un-pools the residual itself (diagan_avgpool2_bwd)."""
     if Hi % 2 or Wi % 2 or _os.environ.get("DIAGAN_RES_UNPOOL", "1") == "0":
         return False
-    Ho, Wo = geom.out_hw(Hi, Wi)
-    sy, dr, off, up = geom.dgrad_params()
     ws = _splitk_ws(torch.device('cuda', torch.cuda.current_device()))
-    return nat.fn("diagan_conv_gemm_pick_cfg_geom")(B, Ho, Wo, geom.Co, Hi, Wi, geom.Ci, geom.R, geom.S, sy, dr, off, up, geom.Kd, 1,
-                                                    ws.numel()) in (9, 13)
+    return nat.fn("diagan_conv_gemm_pick_cfg_geom")(*geom.abi_dgrad(B, Hi, Wi), 1, ws.numel()) in (9, 13)
 
 
 def unpool_fused(geom, B, Hi, Wi):
     """Will conv_dgrad(geom, dy_pooled, ..., unpool=True) run for a layer with input [B,Hi,Wi,Ci]?  (tile_cfg 12: the
     data-gradient through the average pool from nine Winograd products; else the caller up-samples the gradient with
     diagan_avgpool2_bwd and takes the ordinary data-gradient.)"""
-    Ho, Wo = geom.out_hw(Hi, Wi)
-    sy, dr, off, up = geom.dgrad_params()
     ws = _splitk_ws(torch.device('cuda', torch.cuda.current_device()))
-    # the data-gradient gathers from the layer's OUTPUT tensor: its channels are the GEMM's K, the layer's inputs its columns
-    return bool(nat.fn("diagan_conv_wino_unpool_supported")(B, Ho, Wo, geom.Co, Hi, Wi, geom.Ci, geom.R, geom.S, sy, dr, off, up,
-                                                            ws.numel()))
+    return bool(nat.fn("diagan_conv_wino_unpool_supported")(*geom.abi_dgrad(B, Hi, Wi)[:13], ws.numel()))
 
 
 _slabs = {}
@@ -636,12 +627,19 @@ def _slab(dev, nfloat):
     return s
 
 
+def _wgrad_geo(geom, dy_shape, xs):
+    """the geometry list of a weight gradient: the output size is dy's, the gathered tensor's `xs` is wg_x_shape(x, pro)"""
+    if xs[3] != geom.Ci or dy_shape[3] != geom.Co:
+        raise RuntimeError(f"conv_wgrad: x has {xs[3]} channels and dy {dy_shape[3]}, the layer has {geom.Ci} and {geom.Co}")
+    return geom.abi_fwd(dy_shape[0], xs[1], xs[2], (dy_shape[1], dy_shape[2]))
+
+
 def conv_wgrad(geom, dy, x, grad, accumulate, pro=None, sn=None):
     """grad[Co][Kp] (+)= d(loss)/d(Wp) given dy and the layer input x (prologue recomputed).
 
     sn = (W_master, u, v, state): backward through W/sigma (diagan_sn_grad_fix)."""
-    B, Ho, Wo, Co = dy.shape
-    _, Hi, Wi, Ci = wg_x_shape(x, pro)
+    geo = _wgrad_geo(geom, dy.shape, wg_x_shape(x, pro))
+    B, Hi, Wi, Ci, Ho, Wo, Co = geo[:7]
     mode, scale, shift = _pro3(pro)
     for t, n in ((dy, 'dy'), (x, 'x'), (grad, 'grad'), (scale, 'pro_scale'), (shift, 'pro_shift')):
         _chk(t, n)
@@ -650,14 +648,13 @@ def conv_wgrad(geom, dy, x, grad, accumulate, pro=None, sn=None):
     n_elem = Co * geom.Kp
     extra = n_elem if sn is not None else 0
     slab = _slab(dy.device, splits * n_elem + extra)
-    sy, dr, off, up = geom.fwd_params()
     st = nat.current_stream()
     timed = TIMER is not None and TIMER.wants_any()
-    kn = _wgrad_kernel_name(Co, geom.Kp, mode, Ho, Wo, wino=wgrad_uses_wino(geom, Hi, Wi, Ho, Wo),
-                            x3=wgrad_uses_x3(geom, B, Hi, Wi, Ho, Wo, mode, -1)) if timed else None
+    kn = wgrad_kernel_name(Co, geom.Kp, mode, Ho, Wo, wino=wgrad_uses_wino(geom, Hi, Wi, Ho, Wo),
+                           x3=wgrad_uses_x3(geom, B, Hi, Wi, Ho, Wo, mode, -1)) if timed else None
     t0 = TIMER.begin(kn) if timed else None
     nat.call("diagan_conv_wgrad", nat.ptr(dy), nat.ptr(x), nat.ptr(slab), splits, 1, n_elem, -1, nat.ptr(scale), nat.ptr(shift),
-             mode, B, Hi, Wi, Ci, Ho, Wo, Co, geom.R, geom.S, sy, dr, off, up, geom.Kp, st)
+             mode, *geo, st)
     if t0 is not None:
         TIMER.end(kn, 2.0 * M * Co * geom.R * geom.S * Ci, t0,
                   (M, Co, geom.R * geom.S * Ci, f"pro{mode} x{splits}"))
@@ -682,21 +679,17 @@ def wgrad_splits(M, Co, Kp):
 
 def wgrad_splits_geom(geom, B, Hi, Wi, Ho, Wo):
     """split count for this layer geometry (the Winograd weight gradient has its own policy)"""
-    sy, dr, off, up = geom.fwd_params()
-    return nat.fn("diagan_conv_wgrad_splits_geom")(B, Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up,
-                                                   geom.Kp)
+    return nat.fn("diagan_conv_wgrad_splits_geom")(*geom.abi_fwd(B, Hi, Wi, (Ho, Wo)))
 
 
 def wgrad_uses_wino(geom, Hi, Wi, Ho, Wo):
-    sy, dr, off, up = geom.fwd_params()
-    return bool(nat.fn("diagan_conv_wgrad_uses_wino")(Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up,
-                                                      geom.Kp))
+    return bool(nat.fn("diagan_conv_wgrad_uses_wino")(*geom.abi_fwd(0, Hi, Wi, (Ho, Wo))[1:]))
 
 
 def small_co_wgrad(geom):
     """True if the layer's weight gradient has the dedicated 4-output-channel kernel."""
-    sy, dr, off, up = geom.fwd_params()
-    return bool(nat.fn("diagan_conv3x3_co4_wgrad_supported")(geom.Ci, geom.Co, geom.R, geom.S, sy, dr, off, up)
+    # (a query without sizes: Ci, then Co, R, S and the gather parameters)
+    return bool(nat.fn("diagan_conv3x3_co4_wgrad_supported")(geom.Ci, *geom.abi_fwd(0, 0, 0, (0, 0))[6:13])
                 and geom.Kp == 9 * geom.Ci)
 
 
@@ -709,10 +702,9 @@ def conv_wgrad_into(geom, dy, x, slab, splits, stride, bias_off, pro=None, segme
     splits is done later for all layers at once (diagan_wgrad_finish_batched).
     pooled: this launch is ConvLayer.wgrad_pooled's strided form of a stride-1 layer's weight gradient (the kernel timer
     then books the reference convolution's FLOP, 4x what the launch executes, under a marked kernel name)."""
-    B, Ho, Wo, Co = dy.shape
-    _, Hi, Wi, Ci = wg_x_shape(x, pro)
+    geo = _wgrad_geo(geom, dy.shape, wg_x_shape(x, pro))
+    B, Hi, Wi, Ci, Ho, Wo, Co = geo[:7]
     mode, scale, shift = _pro3(pro)
-    sy, dr, off, up = geom.fwd_params()
     if segments == 1 and small_co_wgrad(geom):
         if splits != small_co_wgrad_splits(B, Ho):
             raise RuntimeError(f"conv_wgrad_into: slab has {splits} splits, the 4-channel kernel writes "
@@ -724,31 +716,26 @@ def conv_wgrad_into(geom, dy, x, slab, splits, stride, bias_off, pro=None, segme
             TIMER.end("conv3x3_co4_wgrad_kernel", 2.0 * B * Ho * Wo * Co * 9 * Ci, t0, (B * Ho * Wo, Co, 9 * Ci, f"pro{mode}"))
         return
     timed = TIMER is not None and TIMER.wants_any()
-    kn = _wgrad_kernel_name(Co, geom.Kp, mode, Ho, Wo, wino=wgrad_uses_wino(geom, Hi, Wi, Ho, Wo),
-                            x3=wgrad_uses_x3(geom, B, Hi, Wi, Ho, Wo, mode, bias_off)) if timed else None
-    if kn is not None and pooled:
-        kn += POOLED_TAG
+    kn = wgrad_kernel_name(Co, geom.Kp, mode, Ho, Wo, wino=wgrad_uses_wino(geom, Hi, Wi, Ho, Wo),
+                           x3=wgrad_uses_x3(geom, B, Hi, Wi, Ho, Wo, mode, bias_off), pooled=pooled) if timed else None
     t0 = TIMER.begin(kn) if timed else None
     nat.call("diagan_conv_wgrad", nat.ptr(dy), nat.ptr(x), nat.ptr(slab), splits, segments, stride, bias_off, nat.ptr(scale),
-             nat.ptr(shift), mode, B, Hi, Wi, Ci, Ho, Wo, Co, geom.R, geom.S, sy, dr, off, up, geom.Kp,
-             nat.current_stream())
+             nat.ptr(shift), mode, *geo, nat.current_stream())
     if t0 is not None:
         px = B * Ho * Wo * (4 if pooled else 1)
         TIMER.end(kn, 2.0 * px * Co * geom.R * geom.S * Ci, t0, (px, Co, geom.R * geom.S * Ci, f"pro{mode}"))
 
 
-# ---- the Winograd weight gradients of several layers in ONE launch (include/diagan_hip.h: diagan_conv_wgrad_batched, round 5) ----
+# ---- the weight gradients of several layers in ONE launch (include/diagan_hip.h: diagan_conv_wgrad_batched, round 5) ----
 # A layer's own launch fills the chip by cutting its pixel range 256 / tiles ways: for the small maps that is 4-16 K-steps per
 # workgroup behind ~15 us of fixed cost, and 38 MB of slab per layer whatever its size.  Deferred to the end of the backward
-# pass the layers of one prologue mode share the chip's workgroups in proportion to their work (`batched_wgrad_splits`).
+# pass the layers of one kernel template share the chip's workgroups in proportion to their work (`batched_wgrad_splits`).
 # DIAGAN_WGRAD_BATCH=0: every layer launches on its own, as before.
+# EVERY batchable layer is batched.  Letting a layer whose own launch runs at least N K-steps per workgroup launch on its own was
+# measured on MI355X and is gone (SNGAN-32 / SNGAN-64 images/s): N = 12 -> 4994 / 2876, 24 -> 5053 / 2916, 40 -> 5061 / 2920,
+# everything batched 5074 / 2949 -- the long layers' batched launches are a little slower than their own (the generator's three big
+# layers: 0.92 -> 1.03 ms), the slabs and launches saved are worth more.
 WGRAD_BATCH = _os.environ.get("DIAGAN_WGRAD_BATCH", "1") != "0"
-# a layer whose OWN launch would run at least this many K-steps per workgroup launches on its own; default: never -- sweep on
-# MI355X (tools/probe/wgrad_minsteps.sh; SNGAN-32 / SNGAN-64 images/s): 12 -> 4994 / 2876, 24 -> 5053 / 2916, 40 -> 5061 / 2920,
-# everything batched 5074 / 2949: the long layers' batched launches are a little slower than their own, the slabs and launches
-# saved are worth more
-WGRAD_BATCH_MIN_STEPS = int(_os.environ.get("DIAGAN_WGRAD_BATCH_MIN_STEPS", str(1 << 30)))
-_WG_JOB = None
 
 
 def batched_wgrad_splits(jobs, slots=256, fixed=8.0):
@@ -777,59 +764,90 @@ def batched_wgrad_splits(jobs, slots=256, fixed=8.0):
         per = max(per + 1, per * 1.08)
 
 
-_WG_TABS = {}
+# What WgradBatch (models/layers.py) queues and plans.  WgradShape: all that the plan of a queued weight gradient depends on, no
+# tensor among it (x_shape: of the tensor the kernel gathers from, wg_x_shape; own_splits: of the layer's own chip-filling launch).
+WgradShape = _namedtuple("WgradShape", "geom dy_shape x_shape mode segments own_splits pooled")
+# A queued launch: the layer, its tensors and prologue, its slab entry (slab, splits, stride, bias_off) and its WgradShape
+WgradJob = _namedtuple("WgradJob", "layer dy x pro entry shape")
+# One launch of the plan: positions in the queue and their split counts.  One job: its own launch (conv_wgrad_into) with the
+# layer's own split count; more: one diagan_conv_wgrad_batched launch timed as `kernel_name`.
+WgradLaunch = _namedtuple("WgradLaunch", "cls pooled jobs splits kernel_name")
 
 
-def conv_wgrad_batched(jobs, key=None, kernel_name=None, flop_scale=1.0, cache=None):
-    """jobs: [(geom, dy, x, slab, splits, stride, bias_off, pro, segments)] -- the arguments of conv_wgrad_into, every job a
-    layer of the Winograd weight gradient, all with the same prologue mode; at most wgrad_batch_max() of them.
-    key: a hashable that identifies everything but the tensors' addresses (layers, shapes, splits): the job table's constant
-    columns are then built once and only the five pointers per job are refreshed (host time matters on launch-bound nets)."""
+def wgrad_launch_plan(shapes):
+    """The launches of a queue of batchable weight gradients [WgradShape], in launch order: one per kernel template (batch class;
+    the pooled layers' strided form apart, for the FLOP accounting) and per wgrad_batch_max() layers, every layer with the split
+    count batched_wgrad_splits gives it in its group; a group of one is an ordinary launch.  Host arithmetic and the library's
+    host-only queries: no tensor, no device."""
+    groups = {}
+    for j, s in enumerate(shapes):
+        cls = wgrad_batch_class(s.geom, s.x_shape[1], s.x_shape[2], s.dy_shape[1], s.dy_shape[2], s.mode)
+        groups.setdefault((cls, s.pooled), []).append(j)
+    nmax, plan = wgrad_batch_max(), []
+    for (cls, pooled), grp in groups.items():
+        for lo in range(0, len(grp), nmax):
+            part = tuple(grp[lo: lo + nmax])
+            if len(part) == 1:
+                plan.append(WgradLaunch(cls, pooled, part, (shapes[part[0]].own_splits,), None))
+                continue
+            desc = [wgrad_batch_shape(shapes[j].geom, *shapes[j].dy_shape[:3], cls) for j in part]
+            splits = batched_wgrad_splits([(tiles, steps, shapes[j].segments) for (tiles, steps, _, _), j in zip(desc, part)],
+                                          *desc[-1][2:])
+            s0 = shapes[part[0]]
+            name = wgrad_kernel_name(s0.geom.Co, s0.geom.Kp, s0.mode, s0.dy_shape[1], s0.dy_shape[2], wino=cls < 1000,
+                                     batched=True, pooled=pooled)
+            plan.append(WgradLaunch(cls, pooled, part, tuple(splits), name))
+    return plan
+
+
+_WG_JOB = None
+
+
+def conv_wgrad_batched(jobs, kernel_name, flop_scale=1.0, key=None, cache=None):
+    """jobs: [WgradJob] -- what conv_wgrad_into would be handed for each, every job a layer of ONE batch class (so: one kernel
+    template, one prologue mode); at most wgrad_batch_max() of them.  kernel_name: the launch's name for the kernel timer.
+    key, cache: a hashable that identifies everything but the tensors' addresses (layers, shapes, splits) and the caller's table
+    cache: the job table's constant columns are built once and only the five pointers per job are refreshed (host time matters
+    on launch-bound nets).  WgradBatch keeps one cache per network: it dies with the net, so no id in `key` is recycled."""
     global _WG_JOB
     import numpy as np
     if _WG_JOB is None:
         _WG_JOB = np.dtype([('p', np.uint64, 5), ('l', np.int64, 2), ('i', np.int32, 18)])
         assert _WG_JOB.itemsize == 128
-    # `cache`: the CALLER's table cache (WgradBatch keeps one per network: it dies with the net, so the layer ids in `key` cannot be
-    # recycled under it -- ADVICE r5).  Without one the module-level cache is used and everything the cached constant columns hold
-    # becomes part of the key (a new layer with an old id and another geometry then builds its own table).
-    tabs = cache if cache is not None else _WG_TABS
-    if key is not None and cache is None:
-        key = (key,) + tuple((g.kind, g.Ci, g.Co, g.R, g.S, g.stride, g.pad, g.Kp, tuple(dy.shape), tuple(x.shape), sp, st, bo,
-                              _pro3(pro)[0], seg) for g, dy, x, _, sp, st, bo, pro, seg in jobs)
-    cached = tabs.get(key) if key is not None else None
+    cached = cache.get(key) if cache is not None else None
     if cached is None:
         tab = np.zeros(len(jobs), dtype=_WG_JOB)
         flop, px, mode0 = 0.0, 0, None
-        for j, (geom, dy, x, slab, splits, stride, bias_off, pro, segments) in enumerate(jobs):
-            B, Ho, Wo, Co = dy.shape
-            _, Hi, Wi, Ci = wg_x_shape(x, pro)
-            mode = _pro3(pro)[0]
+        for j, job in enumerate(jobs):
+            e, s = job.entry, job.shape
+            geo = _wgrad_geo(s.geom, s.dy_shape, s.x_shape)
+            B, Hi, Wi, Ci, Ho, Wo, Co, R, S = geo[:9]
+            mode = _pro3(job.pro)[0]
             mode0 = mode if mode0 is None else mode0
-            sy, dr, off, up = geom.fwd_params()
-            tab[j]['l'] = [stride, bias_off]
-            tab[j]['i'] = [splits, segments, mode, B, Hi, Wi, Ci, Ho, Wo, Co, geom.R, geom.S, sy, dr, off, up, geom.Kp, 0]
-            flop += 2.0 * B * Ho * Wo * Co * geom.R * geom.S * Ci
+            tab[j]['l'] = [e.stride, e.bias_off]
+            tab[j]['i'] = [e.splits, s.segments, mode, *geo, 0]
+            flop += 2.0 * B * Ho * Wo * Co * R * S * Ci
             px += B * Ho * Wo
         cached = (tab, flop, px, mode0)
-        if key is not None:
-            if len(tabs) > 256:
-                tabs.clear()
-            tabs[key] = cached
+        if cache is not None:
+            if len(cache) > 256:
+                cache.clear()
+            cache[key] = cached
     tab, flop, px, mode0 = cached
     ptrs = []
-    for geom, dy, x, slab, splits, stride, bias_off, pro, segments in jobs:
+    for job in jobs:
+        pro = job.pro
         scale, shift = (pro[1], pro[2]) if pro is not None and len(pro) > 2 else (None, None)
-        ptrs.append((dy.data_ptr(), x.data_ptr(), slab.data_ptr(), 0 if scale is None else scale.data_ptr(),
+        ptrs.append((job.dy.data_ptr(), job.x.data_ptr(), job.entry.slab.data_ptr(), 0 if scale is None else scale.data_ptr(),
                      0 if shift is None else shift.data_ptr()))
     tab['p'] = ptrs
     timed = TIMER is not None and TIMER.wants_any()
-    kn = (kernel_name or f"conv_wgrad_wino_batched_kernel<{mode0}>") if timed else None
-    t0 = TIMER.begin(kn) if timed else None
+    t0 = TIMER.begin(kernel_name) if timed else None
     nat.call("diagan_conv_wgrad_batched", tab.ctypes.data, len(jobs), nat.current_stream())
     if t0 is not None:
-        g0 = jobs[0][0]
-        TIMER.end(kn, flop * flop_scale, t0, (int(px * flop_scale), g0.Co, g0.R * g0.S * g0.Ci, f"pro{mode0} {len(jobs)} layers"))
+        g0 = jobs[0].shape.geom
+        TIMER.end(kernel_name, flop * flop_scale, t0,
+                  (int(px * flop_scale), g0.Co, g0.R * g0.S * g0.Ci, f"pro{mode0} {len(jobs)} layers"))
 
 
 def wgrad_batch_max():
@@ -838,8 +856,7 @@ def wgrad_batch_max():
 
 def wgrad_batch_class(geom, Hi, Wi, Ho, Wo, mode):
     """identity of the kernel template a layer's weight gradient runs on (0: not batchable); equal classes share a launch"""
-    sy, dr, off, up = geom.fwd_params()
-    return nat.fn("diagan_conv_wgrad_batch_class")(Hi, Wi, geom.Ci, Ho, Wo, geom.Co, geom.R, geom.S, sy, dr, off, up, geom.Kp, mode)
+    return nat.fn("diagan_conv_wgrad_batch_class")(*geom.abi_fwd(0, Hi, Wi, (Ho, Wo))[1:], mode)
 
 
 def wgrad_batch_shape(geom, B, Ho, Wo, cls):
@@ -847,33 +864,36 @@ def wgrad_batch_shape(geom, B, Ho, Wo, cls):
     batched launch of class `cls` -- the inputs of batched_wgrad_splits"""
     if cls < 1000:                          # Winograd: 64 x 64 tiles, 8 tiles of 2x2 outputs per K-step, one workgroup per CU
         return ((geom.Co + 63) // 64) * ((geom.Ci + 63) // 64), (B * (Ho // 2) * (Wo // 2) + 7) // 8, 256, 8.0
-    bn, bk = (64 if geom.Co <= 64 else 128), (64 if geom.Kp <= 64 else 128)
-    if bn == 128 and bk == 64:
-        bn = 64
-    slots = _WG_SLOTS64 if (bn == 64 and bk == 64) else 512
-    return ((geom.Co + bn - 1) // bn) * ((geom.Kp + bk - 1) // bk), (B * Ho * Wo + 31) // 32, slots, 6.0
+    bn, bk = wgrad_tile(geom.Co, geom.Kp)
+    # 512 workgroup slots for every tile.  The chip holds four of the 64 x 64 tile per CU (84 registers, 32 KB of LDS), but planning
+    # it for 1024 / 1280 is not faster: SNGAN-32 5277-5283 / 5277-5280 / 5259-5266 images/s, SNGAN-64 3033-3048 / 3030-3035 /
+    # 3010-3013 for 512 / 1024 / 1280 on one box
+    return ((geom.Co + bn - 1) // bn) * ((geom.Kp + bk - 1) // bk), (B * Ho * Wo + 31) // 32, 512, 6.0
 
 
-# workgroup slots the split policy assumes for the 64 x 64 weight-gradient tile.  The chip holds four of them per CU (84
-# registers, 32 KB of LDS), but planning for 1024 / 1280 is not faster: SNGAN-32 5277-5283 / 5277-5280 / 5259-5266 images/s,
-# SNGAN-64 3033-3048 / 3030-3035 / 3010-3013 for 512 / 1024 / 1280 on one box
-_WG_SLOTS64 = int(_os.environ.get("DIAGAN_WGRAD_SLOTS64", "512"))
 POOLED_TAG = " [pooled gradient]"     # kernel-timer name suffix of ConvLayer.wgrad_pooled's launches
 
 
-def _wgrad_kernel_name(Co, Kp, mode=0, Ho=0, Wo=0, wino=False, x3=False):
-    """Kernel name as rocprofv3 prints it (template arguments BNn, BNk, PRO, P2)."""
-    if wino:
-        return f"conv_wgrad_wino_kernel<{mode}>"
-    if x3:
-        return "conv_wgrad_x3_kernel"
+def wgrad_tile(Co, Kp):
+    """(BNn, BNk) of the implicit-GEMM weight-gradient kernels: the mirror of wgrad_tile in csrc/conv_wgrad.hip"""
     bn, bk = (64 if Co <= 64 else 128), (64 if Kp <= 64 else 128)
-    if bn == 128 and bk == 64:
-        bn = 64
+    return (64, 64) if bk == 64 else (bn, bk)       # (there is no <128,64> instantiation)
+
+
+def wgrad_kernel_name(Co, Kp, mode=0, Ho=0, Wo=0, wino=False, x3=False, batched=False, pooled=False):
+    """Kernel name of a weight-gradient launch as rocprofv3 prints it (template arguments BNn, BNk, PRO, P2).  batched: the launch is
+    diagan_conv_wgrad_batched's; pooled: it is ConvLayer.wgrad_pooled's strided form, marked for the kernel timer (POOLED_TAG)."""
+    tag = POOLED_TAG if pooled else ""
+    if wino:
+        return f"conv_wgrad_wino_{'batched_' if batched else ''}kernel<{mode}>" + tag
+    if x3:
+        return "conv_wgrad_x3_kernel" + tag
+    bn, bk = wgrad_tile(Co, Kp)
+    stem = "conv_wgrad_batched_kernel" if batched else "conv_wgrad_kernel"
     if bk != 128:
-        return f"conv_wgrad_kernel<{bn},{bk},-1,false>"
+        return f"{stem}<{bn},{bk},-1,false>" + tag
     p2 = Ho > 0 and Wo > 0 and (Ho & (Ho - 1)) == 0 and (Wo & (Wo - 1)) == 0
-    return f"conv_wgrad_kernel<{bn},128,{mode},{'true' if p2 else 'false'}>"
+    return f"{stem}<{bn},128,{mode},{'true' if p2 else 'false'}>" + tag
 
 
 def sn_power_iter(W, u_buffer, sigma_buffer, training=True, eps=1e-12):

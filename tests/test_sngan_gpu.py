@@ -717,6 +717,39 @@ def test_batched_weight_gradient_launches_equal_the_per_layer_ones(dataset):
             l2close(out[True][2][k], v, 2e-3, f"G grad {k}", floor=1e-6)
 
 
+@pytest.mark.parametrize("dataset", ["cifar10", "celeba"])
+def test_weight_gradient_launches_are_the_recorded_ones(dataset):
+    """tests/golden/wgrad_plan.json (see tests/test_wgrad_plan_host.py) was recorded from this very step -- the set-up of the test
+    above, one D update and one G update -- before WgradBatch's plan became a function of the queue's shapes.  The weight-gradient
+    launches the kernel timer sees (name, shape tag, FLOP, in order), the integers of every layer's slab entry afterwards and the
+    count of batched launches are the recorded ones exactly: split counts fix the order of the fp32 sums."""
+    import json
+    import os
+    from diagan.ops import conv as C
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_plan.json")))[dataset]
+    res = 32 if dataset == "cifar10" else 64
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand(64, 3, res, res, generator=g) * 2 - 1
+    zd, zg = torch.randn(64, 128, generator=g), torch.randn(64, 128, generator=g)
+    (_, _, _, _), (netG, netD, optG, optD) = build(dataset, "ns")
+    C.TIMER = C.KernelTimer()
+    try:
+        netD.train_step(real_batch=(x.cuda(), None), netG=netG, optD=optD, log_data=Log(), device='cuda', noise=zd.cuda())
+        n_d = len(C.TIMER.records)
+        netG.train_step(real_batch=(x.cuda(), None), netD=netD, optG=optG, log_data=Log(), device='cuda', noise=zg.cuda())
+        records = list(C.TIMER.records)
+    finally:
+        C.TIMER = None
+    for tag, net, recs in (("netD", netD, records[:n_d]), ("netG", netG, records[n_d:])):
+        got = [[name, list(shape), flop] for name, flop, _, _, shape in recs if name.startswith(("conv_wgrad", "conv3x3_co4_wgrad"))]
+        assert got == want[tag]["timer"], tag
+        names = {m: n for n, m in net.named_modules()}
+        entries = [[names[layer], slot, {k: getattr(e, k) for k in ("splits", "own_splits", "segments", "stride", "bias_off", "n_elem")}]
+                   for (layer, slot), e in net.wgrad_batch.entries.items()]
+        assert entries == want[tag]["entries"], tag
+        assert net.wgrad_batch.batched_launches == want[tag]["batched_launches"], tag
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dataset", ["cifar10", "celeba"])
 def test_box_sums_in_the_weight_gradients_loader_change_no_bit(dataset):
