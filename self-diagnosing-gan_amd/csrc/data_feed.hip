@@ -20,6 +20,7 @@
 // In-range indices and in-range tables are preconditions the Python wrappers establish on the host (diagan/datasets/device.py).
 // No allocation, no synchronisation; everything runs on the caller's stream.
 #include "common.h"
+#include "data_feed.h"
 #include "diagan_data.h"
 
 #include <algorithm>
@@ -127,6 +128,15 @@ __global__ __launch_bounds__(DF_T) void data_resize_crop_kernel(const uint8_t* _
 }
 
 static FuncAttrLatch g_resize_lds;
+
+// The address of kFetchTable on the current device, for the kernels of image_feed.hip: they write the same 256 values and read
+// them from this one table (a __constant__ of another translation unit is not visible to them without relocatable device code).
+hipError_t fetch_table_device(const float** table) {
+  void* p = nullptr;
+  hipError_t e = hipGetSymbolAddress(&p, HIP_SYMBOL(kFetchTable));
+  *table = reinterpret_cast<const FetchTable*>(p)->v;
+  return e;
+}
 
 }  // namespace diagan
 

@@ -117,11 +117,13 @@ class _Indices(data.Dataset):
         return index
 
 
-def index_loader(n, batch_size, sampler=None):
+def index_loader(n, batch_size, sampler=None, drop_last=False):
     """The index stream of a loader over n items: a real torch DataLoader over the indices, so the global CPU generator is
     consumed exactly as by the loader it stands for -- a base seed per iter(), then the sampler's own draws -- which the trainer's
-    snapshot logic and phase-2 sampling depend on (trainer.py `_get_logit`).  Yields int64 CPU tensors, ragged last batch."""
-    return data.DataLoader(_Indices(n), batch_size=batch_size, shuffle=sampler is None, sampler=sampler, num_workers=0)
+    snapshot logic and phase-2 sampling depend on (trainer.py `_get_logit`).  Yields int64 CPU tensors, ragged last batch unless
+    `drop_last`."""
+    return data.DataLoader(_Indices(n), batch_size=batch_size, shuffle=sampler is None, sampler=sampler, num_workers=0,
+                           drop_last=drop_last)
 
 
 class DeviceLoader:

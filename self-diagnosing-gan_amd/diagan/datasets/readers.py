@@ -5,6 +5,7 @@ Each reader returns (uint8 [N,H,W,C] at the SOURCE size, int64 targets [N]); `av
 color_mnist.py:26-45,66-88,111-123 and mnist_fmnist.py:24-45,66-88,112-116: the same draws from NumPy's global generator in the
 same order, and the same cache directory of three pickles, so a dataset built by either program serves both.
 """
+import contextlib
 import gzip
 import os
 import pickle
@@ -195,21 +196,29 @@ def _decode(paths):
     return np.stack(out)
 
 
+@contextlib.contextmanager
+def decode_pool(workers=None):
+    """The `map` of a process pool of `workers` processes (None: one per CPU, at most 16), in order; the builtin map when one
+    worker.  PIL decode is what it is for: CelebA here, the StyleGAN2 image folders in datasets/image_loader.py."""
+    from concurrent.futures import ProcessPoolExecutor
+    workers = min(16, os.cpu_count() or 1) if workers is None else workers
+    if workers <= 1:
+        yield map
+        return
+    with ProcessPoolExecutor(max_workers=workers) as pool:
+        yield pool.map
+
+
 def celeba_chunks(root, names, chunk=2048, workers=None):
     """Decoded uint8 [n,Hs,Ws,3] chunks in file order; PIL decode in a process pool of at most 16 workers."""
-    from concurrent.futures import ProcessPoolExecutor
     folder = os.path.join(_celeba_dir(root), 'img_align_celeba')
     paths = [os.path.join(folder, n) for n in names]
     workers = min(16, os.cpu_count() or 1) if workers is None else workers
     piece = max(1, chunk // max(workers, 1))
-    if workers <= 1:
-        for a in range(0, len(paths), chunk):
-            yield _decode(paths[a:a + chunk])
-        return
-    with ProcessPoolExecutor(max_workers=workers) as pool:
+    with decode_pool(workers) as pool_map:
         for a in range(0, len(paths), chunk):
             part = paths[a:a + chunk]
-            yield np.concatenate(list(pool.map(_decode, [part[b:b + piece] for b in range(0, len(part), piece)])))
+            yield np.concatenate(list(pool_map(_decode, [part[b:b + piece] for b in range(0, len(part), piece)])))
 
 
 def read_celeba(root, size=64, resize=None, workers=None, **unused):

@@ -5,9 +5,11 @@ stylegan2/train_ffhq_phase2.py:409-512), phase 1 and phase 2 behind one table.
     python stylegan2/train_ffhq_phase2.py -d ffhq --baseline_exp_name base --resample_score ldr_conf --p1_step 200000 ...
 
 One process per GPU (`python -m torch.distributed.run --nproc-per-node N ...`); rendezvous and the RCCL process group
-come from diagan.trainer.distributed.  There is no lmdb / torchvision in this image: unless a dataset object is
-handed to `main`, images are synthetic tensors of the dataset's resolution served as (image, index) pairs, the item
-format of the reference's MultiResolutionDataset as its trainers consume it."""
+come from diagan.trainer.distributed.  There is no lmdb / torchvision in this image: the real images are a packed
+uint8 file, `<--root>/images_<size>.npy`, written by stylegan2/prepare_data.py and served from HBM by
+diagan.datasets.image_loader.  Where that file is absent, and unless a dataset object is handed to `main`,
+images are synthetic tensors of the dataset's resolution served as (image, index) pairs, the item format of the
+reference's MultiResolutionDataset as its trainers consume it."""
 import argparse
 import os
 import pickle
@@ -93,8 +95,11 @@ class IndexedImages(data.Dataset):
 
 
 def _loader(dataset, args, weights=None):
-    return data.DataLoader(dataset, batch_size=args.batch, drop_last=True,
-                           sampler=TR.data_sampler(dataset, shuffle=True, distributed=args.distributed, weights=weights))
+    sampler = TR.data_sampler(dataset, shuffle=True, distributed=args.distributed, weights=weights)
+    if getattr(dataset, 'resident_images', False):        # the packed set in HBM: flip and fetch in one launch
+        from diagan.datasets.image_loader import FlipLoader
+        return FlipLoader(dataset, args.batch, sampler, drop_last=True)
+    return data.DataLoader(dataset, batch_size=args.batch, drop_last=True, sampler=sampler)
 
 
 def main(phase, argv=None, dataset=None):
@@ -153,7 +158,13 @@ def main(phase, argv=None, dataset=None):
         print(f'start_iter: {args.start_iter}')
 
     if dataset is None:
-        dataset = IndexedImages(args.num_data or 4096, args.size)
+        from diagan.datasets.image_loader import packed_path
+        if os.path.exists(packed_path(args.root, args.size)):
+            from diagan.datasets.image_loader import MultiResolutionDataset
+            print(f'images: {packed_path(args.root, args.size)}')
+            dataset = MultiResolutionDataset(args.root, args.size, device=device)
+        else:
+            dataset = IndexedImages(args.num_data or 4096, args.size)
     weights = None
     if phase == 2:
         from diagan.utils.plot import calculate_scores
