@@ -27,6 +27,9 @@ from diagan.utils.plot import calculate_scores, print_num_params
 from diagan.utils.settings import set_seed
 
 _FLAG = "store_true"     # marker for boolean switches in the tables below
+# not in the reference, which always draws them: they take draws from the global generators (a batch of the loader,
+# np.random.choice), so a run without the flag keeps the random streams it had
+_PICTURES = "also write the reference's pictures (diagan.utils.plot) at the reference's places"
 
 # (option strings, default, type or _FLAG, help)
 SHARED_FLAGS = [
@@ -71,6 +74,7 @@ PHASE2_FLAGS = [
     (("--compat_fetch_quirk",), False, _FLAG, "reproduce mimicry's _fetch_data: an exhausted D_drs iterator restarts on the "
                                               "WEIGHTED main loader (what the reference's runs did after their first "
                                               "epoch); default: D_drs keeps its own uniform loader"),
+    (("--pictures",), False, _FLAG, _PICTURES),
 ]
 # per-dataset phase-1 schedule the reference hard-codes after parsing (train_mimicry_phase1.py:82-92)
 PHASE1_SCHEDULE = {
@@ -217,6 +221,10 @@ def phase2(argv=None):
         return get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None, num_data=args.num_data)
     loader = make_loader(fresh_set(), args.batch_size, args.num_workers, weights=weights)
     loader_drs = make_loader(fresh_set(), args.batch_size, args.num_workers)
+    if args.pictures and weights is not None and run.rank == 0:      # train_mimicry_phase2.py:122-123; no random draw
+        from diagan.utils.plot import show_sorted_score_samples
+        show_sorted_score_samples(loader.dataset, score=weights, save_path=run.save_path, score_name=args.resample_score,
+                                  plot_name=args.exp_name.split('/')[-1])
     print(args)
 
     trainer = LogTrainer(output_path=run.save_path, log_dir=run.out_dir, device=run.device, dataloader=loader,
@@ -252,6 +260,7 @@ COLOR_MNIST_SHARED = [
     (("--num_data",), 10000, int, None),
     (("--resample_score",), None, str, None),
     (("--num_workers",), 0, int, None),             # not in the reference
+    (("--pictures",), False, _FLAG, _PICTURES),
 ]
 COLOR_MNIST_PHASE1 = [
     (("--loss_type",), "ns", str, "loss type"),
@@ -296,9 +305,16 @@ def _plain_weighted_loader(dataset, batch_size, num_workers, weights=None):
     return _loader(dataset, batch_size, sampler, num_workers)
 
 
+def _single_process_pictures(args, run):
+    if args.pictures and run.world > 1:
+        raise NotImplementedError("--pictures draws from the CPU generators the ranks share: single process only, as the "
+                                  "reference's colour-MNIST scripts are")
+
+
 def color_mnist_phase1(argv=None, dataset=None):
     args = color_mnist_phase1_parser().parse_args(argv)
     run = _Run(args)
+    _single_process_pictures(args, run)
     netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, num_pack=args.num_pack,
                                            loss_type=args.loss_type, topk=args.topk == 1)
     print_num_params(netG, netD)
@@ -312,12 +328,16 @@ def color_mnist_phase1(argv=None, dataset=None):
                          vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
                          device=run.device, topk=args.topk, save_logits=args.num_pack == 1, save_eval_logits=False)
     trainer.train()
+    if args.pictures:                                   # train_mimicry_color_mnist_phase1.py:130
+        from diagan.utils.plot import plot_color_mnist_generator
+        plot_color_mnist_generator(netG, save_path=run.save_path, file_name='eval_p1')
     return trainer
 
 
 def color_mnist_phase2(argv=None, dataset=None):
     args = color_mnist_phase2_parser().parse_args(argv)
     run = _Run(args)
+    _single_process_pictures(args, run)
     baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
     netG, netD, netD_drs, optG, optD, optD_drs = get_gan_model(dataset_name=args.dataset, model=args.model, drs=True,
                                                                loss_type=args.loss_type)
@@ -327,7 +347,7 @@ def color_mnist_phase2(argv=None, dataset=None):
     with open(record, "rb") as f:
         logits = pickle.load(f)
     scores = calculate_scores(logits, start_epoch=args.p1_step - 5000, end_epoch=args.p1_step, device=run.device,
-                              keys=None if args.resample_score is None else [args.resample_score])
+                              keys=None if args.resample_score is None or args.pictures else [args.resample_score])
     weights = scores[args.resample_score] if args.resample_score is not None else None
     if weights is not None:
         print(f'sample_weights mean: {weights.mean()}, var: {weights.var()}, max: {weights.max()}, min: {weights.min()}')
@@ -338,6 +358,13 @@ def color_mnist_phase2(argv=None, dataset=None):
                                       major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
     loader = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers, weights=weights)
     loader_drs = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers)
+    prefix = args.exp_name.split('/')[-1]
+    if args.pictures and args.resample_score is not None:      # train_mimicry_color_mnist_phase2.py:119-122, draws included
+        from diagan.utils.plot import plot_data, plot_score_sort
+        imgs = next(iter(loader))[0]
+        plot_data(imgs, num_per_side=8, save_path=run.save_path, file_name=f'{prefix}_resampled_train_data_p2', vis=None)
+        plot_score_sort(loader.dataset, scores, save_path=run.save_path,
+                        phase=f'{prefix}_{args.p1_step - 5000}-{args.p1_step}_score', plot_metric_name=args.resample_score)
     print(args, start['netG'], start['netD'], start['netD'])
     trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
                          optD=optD, optG=optG, netG_ckpt_file=start['netG'], netD_ckpt_file=start['netD'],
@@ -346,12 +373,22 @@ def color_mnist_phase2(argv=None, dataset=None):
                          vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
                          device=run.device, save_logits=False, compat_fetch_quirk=args.compat_fetch_quirk)
     trainer.train()
+    if args.pictures:                                   # train_mimicry_color_mnist_phase2.py:154-164
+        from diagan.models.drs import DRS
+        from diagan.utils.plot import plot_color_mnist_generator
+        plot_color_mnist_generator(netG, save_path=run.save_path, file_name=f'{prefix}-eval_p2')
+        netG_drs = DRS(netG, netD_drs, device=run.device)
+        plot_color_mnist_generator(netG_drs, save_path=run.save_path, file_name=f'{prefix}-eval_drs_percent80_p2')
+        netG.restore_checkpoint(ckpt_file=start['netG'])
+        netG.to(run.device)
+        plot_color_mnist_generator(netG, save_path=run.save_path, file_name=f'{prefix}-eval_generated_p1')
     return trainer
 
 
 # ---- Inclusive GAN baseline (train_mimicry_inclusive.py: flags :46-68, trainer wiring :113-131) ------------------------------
 # The colour-MNIST phase-1 script with `inclusive=True`: the generator gets the loader and the dataset size.  The reference's
-# closing sample plot is left out, as in the other front ends.
+# closing sample plot (:134) is drawn under the keyword `pictures` of inclusive(): this script's flag table is pinned as a whole
+# (tests/test_nn_search_host.py), so unlike the other front ends it has no --pictures on the command line.
 INCLUSIVE_FLAGS = [
     (("--dataset", "-d"), "color_mnist", str, None),
     (("--root", "-r"), "./dataset/colour_mnist", str, "dataset dir"),
@@ -383,8 +420,9 @@ def inclusive_parser():
     return make_parser(INCLUSIVE_FLAGS)
 
 
-def inclusive(argv=None, dataset=None, inception=None):
-    """`inception`: a ready InceptionV3 or weights object in place of --inception_weights (tests)."""
+def inclusive(argv=None, dataset=None, inception=None, pictures=False):
+    """`inception`: a ready InceptionV3 or weights object in place of --inception_weights (tests).  `pictures`: draw the
+    reference's closing sample panels (eval_p1_all / _green / _red .jpg), which take draws from the global generators."""
     args = inclusive_parser().parse_args(argv)
     run = _Run(args)
     if run.world > 1:
@@ -404,4 +442,7 @@ def inclusive(argv=None, dataset=None, inception=None):
                          vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
                          device=run.device, topk=args.topk, save_logits=args.num_pack == 1, save_eval_logits=False)
     trainer.train()
+    if pictures:                                        # train_mimicry_inclusive.py:134
+        from diagan.utils.plot import plot_color_mnist_generator
+        plot_color_mnist_generator(netG, save_path=run.save_path, file_name='eval_p1')
     return trainer

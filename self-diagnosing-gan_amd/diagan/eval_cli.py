@@ -41,6 +41,8 @@ EVAL_FLAGS = [
 ]
 DRS_FLAGS = [
     (("--use_original_netD",), False, _FLAG, None),
+    # not in the reference, which always writes it: the picture takes acceptance draws of its own, so it is asked for
+    (("--pictures",), False, _FLAG, "also write images/fake_samples_step_N_after_drs.png (64 accepted samples)"),
 ]
 # eval_gan_with_index.py:25-42 (the reference has no --root here: it reads ./dataset)
 INDEX_FLAGS = [
@@ -149,7 +151,8 @@ def _main(args, drs):
     common = dict(log_dir=save_path, netG=netG, evaluate_step=args.netG_ckpt_step, num_runs=1, device=device, model=model)
     if drs:
         run = evaluate_drs
-        common.update(netD_drs=netD_drs, use_original_netD=args.use_original_netD, is_stylegan2=args.model == 'stylegan2')
+        common.update(netD_drs=netD_drs, use_original_netD=args.use_original_netD, is_stylegan2=args.model == 'stylegan2',
+                      visualize=args.pictures)
     else:
         run = evaluate
     for m in metrics:
@@ -254,7 +257,8 @@ def _group_setup(args, drs, **model_kwargs):
     common = dict(log_dir=save_path, netG=netG, dataset=dataset, evaluate_step=args.netG_ckpt_step, num_runs=1, device=device,
                   model=model)
     if drs:
-        common.update(netD_drs=netD_drs, use_original_netD=args.use_original_netD, is_stylegan2=args.model == 'stylegan2')
+        common.update(netD_drs=netD_drs, use_original_netD=args.use_original_netD, is_stylegan2=args.model == 'stylegan2',
+                      visualize=args.pictures)
     return common
 
 

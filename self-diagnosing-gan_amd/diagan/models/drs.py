@@ -69,3 +69,16 @@ class DRS(nn.Module):
             rounds.append(accepted)
             have += accepted.size(0)
         return torch.cat(rounds, dim=0)[:num_images]
+
+    def visualize_images(self, log_dir, evaluate_step, num_images=64):
+        """The grid the reference saves after DRS (trainer/evaluate.py:85-95): num_images accepted samples through
+        make_grid(padding=2, normalize=True) and save_image(normalize=True), as
+        log_dir/images/fake_samples_step_{evaluate_step}_after_drs.png.  Takes its own rounds of generation and acceptance draws."""
+        import os
+
+        from diagan.utils.image_grid import save_image
+        img_dir = os.path.join(str(log_dir), 'images')
+        os.makedirs(img_dir, exist_ok=True)
+        path = '{}/fake_samples_step_{}_after_drs.png'.format(img_dir, evaluate_step)
+        save_image(self.generate_images(num_images), path, padding=2, normalize=True, passes=2)
+        return path

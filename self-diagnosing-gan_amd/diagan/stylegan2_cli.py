@@ -60,6 +60,8 @@ COMMON = [
                                                       "behaviour, one seed for all ranks (stylegan2/train_ffhq.py:497)")),
     (("--log_every",), dict(default=100, type=int)),
     (("--checkpoint_every",), dict(default=5000, type=int)),
+    (("--sample_every",), dict(default=0, type=int, help="write the sample grids every N iterations as PNG; 0 = never "
+                                                        "(the reference writes them every 100: --sample_every 100)")),
 ]
 PHASE = {
     1: [(("--r1",), dict(type=float, default=0.1, help="weight of the r1 regularization")),
@@ -180,7 +182,8 @@ def main(phase, argv=None, dataset=None):
         extra['drs_loader'] = _loader(dataset, args)
     loader = _loader(dataset, args, weights)
     trainer = TR.StyleGAN2Trainer(args, loader, generator, discriminator, g_optim, d_optim, g_ema, device, save_path,
-                                  log_every=args.log_every, checkpoint_every=args.checkpoint_every, **extra)
+                                  log_every=args.log_every, checkpoint_every=args.checkpoint_every,
+                                  sample_every=args.sample_every, **extra)
     trainer.train()
     dump = os.environ.get("DIAGAN_SG2_DUMP")        # test hook: final flat parameters of every rank
     if dump:

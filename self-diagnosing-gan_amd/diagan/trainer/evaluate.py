@@ -7,7 +7,8 @@ metrics.evaluate, whose argument checks, file names and JSON layout these keep).
 
 A JSON file maps step -> [score per seed] ({key: [score per seed]} for PR); an existing file is read first and merged, and the
 file is rewritten after every step.  Every metric runs on the HIP engine (fid_score, kid_score, inception_score, pr_score of
-this package); the image grid the reference saves after DRS (torchvision) is not produced.
+this package).  The image grid the reference saves after DRS (evaluate.py:85-95, :249) is written under the keyword
+visualize=True of the evaluate_drs* functions: it takes draws of its own from np.random, so it is off by default.
 
 By group (reference evaluate.py:585-1283): evaluate_with_index / evaluate_drs_with_index write
 fid_{name}[_drs]_{len(index)}_{fake // 1000}k.json (step -> [FID per seed]); evaluate_with_attr / evaluate_drs_with_attr write one
@@ -81,7 +82,7 @@ def _score(metric, netG, seed, device, log_dir, kwargs):
 
 
 def _run(metric, netG, netD_drs, log_dir, evaluate_range, evaluate_step, use_original_netD, num_runs, start_seed, write_to_json_,
-         device, is_stylegan2, kwargs):
+         device, is_stylegan2, kwargs, visualize=False):
     if evaluate_range and evaluate_step or not (evaluate_step or evaluate_range):
         raise ValueError("Only one of evaluate_step or evaluate_range can be defined.")
     if evaluate_range:
@@ -122,6 +123,8 @@ def _run(metric, netG, netD_drs, log_dir, evaluate_range, evaluate_step, use_ori
             else:
                 netD_drs.restore_checkpoint(ckpt_file=os.path.join(netD_ckpt_dir, f'{ckpt_path}_{step}_steps.pth'), optimizer=None)
             sampler = DRS(netG=netG, netD=netD_drs, device=device)
+            if visualize:
+                sampler.visualize_images(log_dir=log_dir, evaluate_step=evaluate_step)
 
         scores = defaultdict(list) if metric == 'pr' else []
         for seed in range(start_seed, start_seed + num_runs):
@@ -162,12 +165,13 @@ def evaluate(metric, netG, log_dir, evaluate_range=None, evaluate_step=None, num
 
 
 def evaluate_drs(metric, netG, netD_drs, log_dir, evaluate_range=None, evaluate_step=None, use_original_netD=False, num_runs=1,
-                 start_seed=0, overwrite=False, write_to_json=True, device=None, is_stylegan2=False, **kwargs):
+                 start_seed=0, overwrite=False, write_to_json=True, device=None, is_stylegan2=False, visualize=False, **kwargs):
     """evaluate() with the generator's samples filtered by discriminator rejection sampling through netD_drs, restored from
     checkpoints/netD_drs (use_original_netD: checkpoints/netD), or with is_stylegan2 from the 'drs_d' (else 'd') entry of the
-    generator's own checkpoint file."""
+    generator's own checkpoint file.  visualize: also write images/fake_samples_step_{evaluate_step}_after_drs.png, 64 accepted
+    samples (DRS.visualize_images), before the scores of each checkpoint as the reference does."""
     return _run(metric, netG, netD_drs, log_dir, evaluate_range, evaluate_step, use_original_netD, num_runs, start_seed,
-                write_to_json, device, is_stylegan2, kwargs)
+                write_to_json, device, is_stylegan2, kwargs, visualize)
 
 
 def evaluate_pr(netG, log_dir, evaluate_range=None, evaluate_step=None, num_runs=1, start_seed=0, overwrite=False,
@@ -212,7 +216,7 @@ def _attr_output_name(metric, attr, kwargs):
     return '{}_{}_{}k_{}k.json'.format(metric, attr, kwargs['num_real_samples'] // 1000, kwargs['num_fake_samples'] // 1000)
 
 
-def _samplers(netG, netD_drs, log_dir, steps, use_original_netD, is_stylegan2, device):
+def _samplers(netG, netD_drs, log_dir, steps, use_original_netD, is_stylegan2, device, visualize_step=None):
     """Yields (step, sampler) for every checkpoint of the range that exists: the restored generator, or DRS around it."""
     netG_ckpt_dir = os.path.join(log_dir, 'checkpoints', 'netG')
     ckpt_path = 'netD' if use_original_netD else 'netD_drs'
@@ -234,11 +238,14 @@ def _samplers(netG, netD_drs, log_dir, steps, use_original_netD, is_stylegan2, d
         else:
             netD_drs.restore_checkpoint(ckpt_file=os.path.join(log_dir, 'checkpoints', ckpt_path, f'{ckpt_path}_{step}_steps.pth'),
                                         optimizer=None)
-        yield step, DRS(netG=netG, netD=netD_drs, device=device)
+        sampler = DRS(netG=netG, netD=netD_drs, device=device)
+        if visualize_step is not None:
+            sampler.visualize_images(log_dir=log_dir, evaluate_step=visualize_step)
+        yield step, sampler
 
 
 def _run_with_index(metric, index, netG, netD_drs, log_dir, evaluate_range, evaluate_step, use_original_netD, num_runs,
-                    start_seed, overwrite, write_to_json_, device, is_stylegan2, kwargs):
+                    start_seed, overwrite, write_to_json_, device, is_stylegan2, kwargs, visualize=False):
     steps = _check_steps(evaluate_range, evaluate_step)
     name = _index_output_name(metric, index, netD_drs is not None, kwargs)
     log_dir = Path(log_dir)
@@ -254,7 +261,8 @@ def _run_with_index(metric, index, netG, netD_drs, log_dir, evaluate_range, eval
     for step in computed:
         print("INFO: FID at step {} has been computed. Skipping...".format(step))
     todo = [s for s in range(steps[0], steps[1] + 1, steps[2]) if s not in computed]
-    for step, sampler in _samplers(netG, netD_drs, log_dir, steps, use_original_netD, is_stylegan2, device):
+    for step, sampler in _samplers(netG, netD_drs, log_dir, steps, use_original_netD, is_stylegan2, device,
+                                  evaluate_step if visualize else None):
         if step not in todo:
             continue
         scores = []
@@ -288,11 +296,11 @@ def evaluate_with_index(metric, index, netG, log_dir, evaluate_range=None, evalu
 
 def evaluate_drs_with_index(metric, index, netG, netD_drs, log_dir, evaluate_range=None, evaluate_step=None,
                             use_original_netD=False, num_runs=3, start_seed=0, overwrite=False, write_to_json=True, device=None,
-                            is_stylegan2=False, **kwargs):
-    """evaluate_with_index() with the samples filtered by discriminator rejection sampling (see evaluate_drs); the file is
-    fid_{name}_drs_{len(index)}_{num_fake_samples // 1000}k.json."""
+                            is_stylegan2=False, visualize=False, **kwargs):
+    """evaluate_with_index() with the samples filtered by discriminator rejection sampling (see evaluate_drs, also for
+    visualize); the file is fid_{name}_drs_{len(index)}_{num_fake_samples // 1000}k.json."""
     return _run_with_index(metric, index, netG, netD_drs, log_dir, evaluate_range, evaluate_step, use_original_netD, num_runs,
-                           start_seed, overwrite, write_to_json, device, is_stylegan2, kwargs)
+                           start_seed, overwrite, write_to_json, device, is_stylegan2, kwargs, visualize)
 
 
 def _attr_scores(metric, attrs, sampler, seed, device, log_dir, kwargs):
@@ -307,7 +315,7 @@ def _attr_scores(metric, attrs, sampler, seed, device, log_dir, kwargs):
 
 
 def _run_with_attr(metric, attr, netG, netD_drs, log_dir, evaluate_range, evaluate_step, use_original_netD, num_runs, start_seed,
-                   overwrite, write_to_json_, device, is_stylegan2, kwargs):
+                   overwrite, write_to_json_, device, is_stylegan2, kwargs, visualize=False):
     from diagan.trainer import group_eval as G
     steps = _check_steps(evaluate_range, evaluate_step)
     kwargs = dict(kwargs)
@@ -330,7 +338,8 @@ def _run_with_attr(metric, attr, netG, netD_drs, log_dir, evaluate_range, evalua
         kwargs['bank'] = G.real_feature_bank(kwargs['dataset'], E.resolve_model(kwargs.get('model')), E.resolve_device(device),
                                              kwargs.get('batch_size', 50), kwargs.pop('feat_file', None))
     label = _ATTR_NAMES[metric]
-    for step, sampler in _samplers(netG, netD_drs, log_dir, steps, use_original_netD, is_stylegan2, device):
+    for step, sampler in _samplers(netG, netD_drs, log_dir, steps, use_original_netD, is_stylegan2, device,
+                                  evaluate_step if visualize else None):
         todo = [a for a in attrs if overwrite or not write_to_json_ or step not in files[a][1]['attr']]
         for a in attrs:
             if a not in todo:
@@ -392,8 +401,8 @@ def evaluate_with_attr(metric, attr, netG, log_dir, evaluate_range=None, evaluat
 
 def evaluate_drs_with_attr(metric, attr, netG, netD_drs, log_dir, evaluate_range=None, evaluate_step=None,
                            use_original_netD=False, num_runs=3, start_seed=0, overwrite=False, write_to_json=True, device=None,
-                           is_stylegan2=False, **kwargs):
-    """evaluate_with_attr() with the samples filtered by discriminator rejection sampling (see evaluate_drs).  As in the
-    reference the files carry the same names as evaluate_with_attr's."""
+                           is_stylegan2=False, visualize=False, **kwargs):
+    """evaluate_with_attr() with the samples filtered by discriminator rejection sampling (see evaluate_drs, also for
+    visualize).  As in the reference the files carry the same names as evaluate_with_attr's."""
     return _run_with_attr(metric, attr, netG, netD_drs, log_dir, evaluate_range, evaluate_step, use_original_netD, num_runs,
-                          start_seed, overwrite, write_to_json, device, is_stylegan2, kwargs)
+                          start_seed, overwrite, write_to_json, device, is_stylegan2, kwargs, visualize)

@@ -62,17 +62,21 @@ class Logger:
         return line
 
     def vis_images(self, netG, global_step, num_images=64):
-        """Fixed-noise sample grid; written as a raw tensor (torchvision is not available)."""
+        """Fixed-noise sample grid: the raw tensor, and beside it the picture mimicry's logger writes from it -- make_grid(padding=2,
+        normalize=True), then save_image(normalize=True) -- tiled on the device (diagan.utils.image_grid).  No draw from a global
+        generator: the noise has a generator of its own."""
         import torch
+        from diagan.utils.image_grid import save_image
         img_dir = os.path.join(self.log_dir, 'images')
         os.makedirs(img_dir, exist_ok=True)
         gen = torch.Generator(device='cpu').manual_seed(0)
         noise = torch.randn((num_images, netG.nz), generator=gen).to(netG.device)
         was_training = netG.training
         netG.eval()
-        images = netG.generate_images(num_images, noise=noise).detach().cpu()
+        images = netG.generate_images(num_images, noise=noise).detach()
         netG.train(was_training)
-        torch.save(images, os.path.join(img_dir, f'fixed_fake_samples_step_{global_step}.pt'))
+        torch.save(images.cpu(), os.path.join(img_dir, f'fixed_fake_samples_step_{global_step}.pt'))
+        save_image(images, os.path.join(img_dir, f'fixed_fake_samples_step_{global_step}.png'), padding=2, normalize=True, passes=2)
 
     def close_writers(self):
         pass

@@ -151,12 +151,13 @@ class StyleGAN2Trainer:
     > 0, else tuned by AdaptiveAugment on D's real logits."""
 
     def __init__(self, args, loader, generator, discriminator, g_optim, d_optim, g_ema, device, output_path,
-                 drs_loader=None, drs_discriminator=None, drs_d_optim=None, log_every=100, checkpoint_every=5000):
+                 drs_loader=None, drs_discriminator=None, drs_d_optim=None, log_every=100, checkpoint_every=5000,
+                 sample_every=0):
         self.args, self.device, self.output_path = args, device, Path(output_path)
         self.loader, self.drs_loader = loader, drs_loader
         self.G, self.D, self.g_ema, self.D_drs = generator, discriminator, g_ema, drs_discriminator
         self.g_optim, self.d_optim, self.drs_d_optim = g_optim, d_optim, drs_d_optim
-        self.log_every, self.checkpoint_every = log_every, checkpoint_every
+        self.log_every, self.checkpoint_every, self.sample_every = log_every, checkpoint_every, sample_every
         self.mean_path_length = 0
         self.mean_path_length_avg = 0
         self.logit_results = defaultdict(dict)
@@ -307,9 +308,37 @@ class StyleGAN2Trainer:
                     if self.augment:
                         line += f"; augment: {self.ada_aug_p:.4f}; rt: {self.r_t_stat:.4f}"
                     print(line)
+            if get_rank() == 0 and self.sample_every > 0 and i % self.sample_every == 0:
+                self.write_samples(i, sample_z)
             if get_rank() == 0 and i > 0 and i % self.checkpoint_every == 0:
                 self.save_checkpoint(i)
         return sample_z
+
+    def write_samples(self, i, sample_z):
+        """The reference's pictures of iteration i (every 100 there; `sample_every` here, 0 = never): g_ema([sample_z]) as
+        sample/NNNNNN.png (train_ffhq.py:350-362) or, in phase 2, as fixed_sample/NNNNNN.png with a freshly drawn batch beside it
+        as random_sample/NNNNNN.png (train_ffhq_phase2.py:359-383).  g_ema's noise maps and the fresh latents come from the
+        device generator, whose state is saved and put back: training is bit-identical with and without pictures."""
+        from diagan.utils.image_grid import save_image
+        a = self.args
+        state = torch.cuda.get_rng_state(self.device)
+        was_training = self.g_ema.training
+        written = []
+        with torch.no_grad():
+            self.g_ema.eval()
+            batches = [('sample', sample_z)] if self.D_drs is None else \
+                [('fixed_sample', sample_z), ('random_sample', None)]
+            for folder, z in batches:
+                if z is None:
+                    z = torch.randn(a.n_sample, a.latent, device=self.device)
+                sample, _ = self.g_ema([z])
+                save_path = self.output_path / folder
+                save_path.mkdir(parents=True, exist_ok=True)
+                written.append(save_path / f"{str(i).zfill(6)}.png")
+                save_image(sample, written[-1], nrow=int(a.n_sample ** 0.5), normalize=True, range=(-1, 1))
+        self.g_ema.train(was_training)
+        torch.cuda.set_rng_state(state, self.device)
+        return written
 
     def save_checkpoint(self, i):
         """same keys as the reference's checkpoint (train_ffhq.py:367-380 / phase2 :389-401)"""

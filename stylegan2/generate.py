@@ -3,9 +3,9 @@
 
     python stylegan2/generate.py --size 256 --ckpt exp_results/base/checkpoint/200000.pt --pics 20 --truncation 0.7
 
-torchvision is not part of this image, so instead of PNG grids every batch is written as a float tensor in [-1, 1]
-(`<out>/<index>.pt`, NCHW), which `torchvision.utils.save_image(..., normalize=True, range=(-1, 1))` turns into the
-reference's picture."""
+Every batch is written as a float tensor in [-1, 1] (`<out>/<index>.pt`, NCHW) and, beside it, as the reference's picture
+`<out>/<index>.png`: `save_image(sample, ..., nrow=1, normalize=True, range=(-1, 1))` (generate.py:20-26), tiled and converted
+on the device by diagan.utils.image_grid."""
 import argparse
 import os
 import sys
@@ -29,6 +29,7 @@ def build_parser():
 
 
 def generate(args, g_ema, device, mean_latent):
+    from diagan.utils.image_grid import save_image
     os.makedirs(args.out, exist_ok=True)
     paths = []
     with torch.no_grad():
@@ -38,6 +39,7 @@ def generate(args, g_ema, device, mean_latent):
             sample, _ = g_ema([sample_z], truncation=args.truncation, truncation_latent=mean_latent)
             paths.append(os.path.join(args.out, f"{str(i).zfill(6)}.pt"))
             torch.save(sample.clamp(-1, 1).cpu(), paths[-1])
+            save_image(sample, os.path.join(args.out, f"{str(i).zfill(6)}.png"), nrow=1, normalize=True, range=(-1, 1))
     return paths
 
 
