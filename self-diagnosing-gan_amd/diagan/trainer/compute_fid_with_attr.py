@@ -19,7 +19,7 @@ def fid_scores_with_attrs(attrs, num_fake_samples, netG, dataset, seed=0, device
     groups = G.attr_groups(root, attrs, G.dataset_rows(dataset) if bank is None else bank.shape[0], num_samples, verbose)
     if bank is None:
         bank = G.real_feature_bank(dataset, model, device, batch_size, feat_file, None, verbose)
-    fake = G.fake_features(netG, num_fake_samples, model, device, batch_size, seed, verbose)
+    fake = E.fake_features(netG, num_fake_samples, model, device, batch_size, seed, verbose)
     flat = {(attr, side): idx for attr, pair in groups.items() for side, idx in zip(('attr', 'not_attr'), pair)}
     fids = G.fid_by_group(bank, flat, fake, device)
     out = {}

@@ -30,7 +30,7 @@ def fid_score_with_index(index, num_fake_samples, netG, dataset, seed=0, device=
         bank, rows = G.real_feature_bank(dataset, model, device, batch_size, kwargs.get('feat_file'), index, verbose), None
     else:
         rows = index
-    fake = G.fake_features(netG, num_fake_samples, model, device, batch_size, seed, verbose)
+    fake = E.fake_features(netG, num_fake_samples, model, device, batch_size, seed, verbose)
     group = np.arange(bank.shape[0]) if rows is None else rows
     score = G.fid_by_group(bank, {kwargs['name']: group}, fake, device)[kwargs['name']]
     if verbose:

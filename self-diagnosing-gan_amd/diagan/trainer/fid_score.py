@@ -14,17 +14,13 @@ def compute_real_dist_stats(num_samples, model, device, batch_size=50, dataset=N
                             log_dir='./log'):
     """(mu, sigma) of the first num_samples real images; loaded from stats_file when it exists, else computed and saved there.
     Without stats_file a dataset NAME caches under log_dir/metrics/fid/statistics; other datasets are not cached."""
-    tag = E.dataset_tag(dataset)
-    synthetic_cache = stats_file is None and tag is not None      # a cache this function computed from a dataset NAME
-    if synthetic_cache:
-        stats_dir = os.path.join(log_dir, 'metrics', 'fid', 'statistics')
-        os.makedirs(stats_dir, exist_ok=True)
-        stats_file = os.path.join(stats_dir, "fid_stats_{}_{}k_run_{}.npz".format(tag, num_samples // 1000, seed))
+    stats_file, synthetic = E.real_cache_file(stats_file, dataset, log_dir, ('fid', 'statistics'), "fid_stats_{}_{}k_run_{}.npz",
+                                              num_samples, seed)
     if stats_file and os.path.exists(stats_file):
         if verbose:
             print("INFO: Loading existing statistics for real images from {}...".format(stats_file))
-            if synthetic_cache:
-                print("WARNING: these statistics were computed from SYNTHETIC stand-in images of '{}'".format(tag))
+            if synthetic:
+                print("WARNING: these statistics were computed from SYNTHETIC stand-in images of '{}'".format(dataset))
         return fid_utils.load_statistics(stats_file)
     if verbose:
         print("INFO: Computing statistics for real images...")
@@ -48,7 +44,7 @@ def fid_score(num_real_samples, num_fake_samples, netG, dataset, seed=0, device=
     model = E.resolve_model(model)
     E.seed_all(seed)
     mu_r, s_r = compute_real_dist_stats(num_real_samples, model, device, batch_size, dataset, stats_file, seed, verbose, log_dir)
-    st = fid_utils.FeatureStatistics(2048, device)
+    st = fid_utils.FeatureStatistics(2048, device)     # streamed batch by batch: E.fake_features would hold 50 000 x 2048 floats
     images = E.fake_images(netG, num_fake_samples, device, batch_size=batch_size, seed=seed, verbose=verbose)
     for f in E.inception_batches(images, model, device, batch_size):
         st.update(f)

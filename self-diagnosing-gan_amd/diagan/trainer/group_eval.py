@@ -1,8 +1,8 @@
 """Evaluation by group: one Inception pass over the real set fills a feature bank; FID, recall and coverage of any
 number of groups of real samples -- all 40 CelebA attributes, the top / bottom-k by phase-1 weight -- reduce from that bank.
 The reference pays one Inception pass per attribute (compute_fid_with_attr.py, pr_score_with_attr.py) and one per index set
-(compute_fid_with_index.py)."""
-import os
+(compute_fid_with_index.py).  The bank's images come through eval_common.real_batches, the reader every metric uses, and its npy
+cache through eval_common's npy_file / load_npy / save_npy, as pr_score.compute_real_features' does."""
 from collections import OrderedDict
 
 import numpy as np
@@ -10,58 +10,9 @@ import torch
 
 from diagan.trainer import eval_common as E
 from diagan.trainer import fid_utils
+from diagan.trainer.eval_common import fake_features         # re-exported: in this module's __all__
 
 __all__ = ['real_feature_bank', 'fid_by_group', 'attr_groups', 'attr_names', 'subsample', 'fake_features']
-
-
-_unit = {}
-
-
-def _unit_table(device):
-    """q / 255 for q = 0..255, divided on the host: a division by a scalar on the device is a multiplication by its reciprocal,
-    one ulp off for some q, and eval_common.real_images -- whose features these must equal -- divides on the host."""
-    key = str(device)
-    if key not in _unit:
-        _unit[key] = (torch.arange(256, dtype=torch.float32) / 255.0).to(device)
-    return _unit[key]
-
-
-def _real_batches(dataset, index, batch_size):
-    """[b, 3, H, W] float32 batches in [0, 1] on the 1/255 grid (eval_common.real_images' values, bit for bit, without its
-    round trip through the host for device-resident images) of the rows `index`
-    (None: all rows, in order) of a Dataset or an [N, 3, H, W] tensor in [-1, 1]; by fetch / fetch_range where the dataset
-    offers them."""
-    if isinstance(dataset, np.ndarray):
-        dataset = torch.as_tensor(dataset)
-    n = len(dataset)
-    if index is not None:
-        index = torch.as_tensor(np.asarray(index, dtype=np.int64)).reshape(-1)
-        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= n):
-            raise IndexError(f"real_feature_bank: index outside [0, {n})")
-    inner = getattr(dataset, 'dataset', None)                       # a WeightedDataset around device-resident images
-    fetch = getattr(dataset, 'fetch', None) or getattr(inner, 'fetch', None)
-    fetch_range = getattr(dataset, 'fetch_range', None)
-    count = n if index is None else index.numel()
-    for lo in range(0, count, batch_size):
-        hi = min(count, lo + batch_size)
-        x = None
-        if isinstance(dataset, torch.Tensor):
-            x = dataset[lo:hi] if index is None else dataset[index[lo:hi]]
-        elif index is None and fetch_range is not None:
-            x = fetch_range(lo, hi)                                 # None: the dataset cannot serve ranges after all
-        elif index is not None and fetch is not None:
-            x = fetch(index[lo:hi])
-        if x is None:
-            rows = range(lo, hi) if index is None else index[lo:hi].tolist()
-            x = torch.stack([torch.as_tensor(it[0] if isinstance(it, (tuple, list)) else it)
-                             for it in (dataset[int(i)] for i in rows)])
-        elif isinstance(x, (tuple, list)):
-            x = x[0]
-        x = x.detach().to(dtype=torch.float32)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"real images must be [N, 3, H, W], got {tuple(x.shape)}")
-        q = (((x + 1.0) * 0.5).clamp_(0, 1) * 255.0 + 0.5).clamp_(0, 255).floor_().long()
-        yield _unit_table(x.device)[q]
 
 
 def real_feature_bank(dataset, model, device, batch_size=50, feat_file=None, index=None, verbose=True):
@@ -73,29 +24,21 @@ def real_feature_bank(dataset, model, device, batch_size=50, feat_file=None, ind
         raise ValueError("real_feature_bank reads images: pass a Dataset or an [N, 3, H, W] tensor, not a dataset name")
     device = E.resolve_device(device)
     n = len(dataset) if index is None else int(np.asarray(index).size)
-    if feat_file is not None and not str(feat_file).endswith('.npy'):
-        feat_file = str(feat_file) + '.npy'
-    if feat_file and os.path.exists(feat_file):
+    feat_file = E.npy_file(feat_file)
+    feats = E.load_npy(feat_file)
+    if feats is not None:
         if verbose:
             print("INFO: Loading existing features for real images from {}...".format(feat_file))
-        feats = np.load(feat_file)
         if feats.shape[0] != n:
             raise ValueError(f"{feat_file} holds {feats.shape[0]} rows, the bank wanted has {n}")
         return torch.as_tensor(feats, dtype=torch.float32).to(device)
     if verbose:
         print("INFO: Computing features for {} real images...".format(n))
     model = E.resolve_model(model)
-    bank = torch.cat(list(E.inception_batches(_real_batches(dataset, index, batch_size), model, device, batch_size)))
+    bank = torch.cat(list(E.inception_batches(E.real_batches(dataset, batch_size, index), model, device, batch_size)))
     if feat_file:
-        os.makedirs(os.path.dirname(os.path.abspath(feat_file)), exist_ok=True)
-        np.save(feat_file, bank.cpu().numpy())
+        E.save_npy(feat_file, bank.cpu().numpy())
     return bank
-
-
-def fake_features(netG, num_samples, model, device, batch_size=50, seed=0, verbose=True):
-    """[n, 2048] float32 device tensor of the features of the generator's samples (eval_common.fake_images' preparation)."""
-    images = E.fake_images(netG, num_samples, device, batch_size=batch_size, seed=seed, verbose=verbose)
-    return torch.cat(list(E.inception_batches(images, model, device, batch_size)))
 
 
 def _stats(features, device):

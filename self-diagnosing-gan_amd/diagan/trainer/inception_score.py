@@ -31,8 +31,7 @@ def inception_score(num_samples, netG, device=None, batch_size=50, splits=10, lo
     device = E.resolve_device(device)
     model = E.resolve_model(model, need_logits=True)
     E.seed_all(seed)
-    images = E.fake_images(netG, num_samples, device, batch_size=batch_size, seed=seed, print_every=print_every, verbose=verbose)
-    logits = torch.cat(list(E.inception_batches(images, model, device, batch_size, what='logits')))
+    logits = E.fake_features(netG, num_samples, model, device, batch_size, seed, verbose, what='logits', print_every=print_every)
     score, std = inception_score_from_logits(logits, splits=splits)
     if verbose:
         print("INFO: Inception Score: {:.4f} ± {:.4f} [Time Taken: {:.4f} secs]".format(score, std, time.time() - start_time))

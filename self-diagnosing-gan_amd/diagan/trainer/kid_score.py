@@ -20,8 +20,7 @@ def kid_score(num_samples, netG, dataset, device=None, num_subsets=50, subset_si
     model = E.resolve_model(model)
     E.seed_all(seed)
     real = torch.cat(list(E.inception_batches(E.real_images(dataset, num_samples, batch_size), model, device, batch_size)))
-    fake = torch.cat(list(E.inception_batches(E.fake_images(netG, num_samples, device, batch_size, seed, verbose=verbose),
-                                              model, device, batch_size)))
+    fake = E.fake_features(netG, num_samples, model, device, batch_size, seed, verbose)
     mmds = kid_utils.polynomial_mmd_averages(fake, real, n_subsets=num_subsets, subset_size=subset_size, device=device)
     score, std = float(np.mean(mmds)), float(np.std(mmds))
     if verbose:

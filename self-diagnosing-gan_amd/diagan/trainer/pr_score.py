@@ -1,10 +1,8 @@
 """Precision / recall of a generator on the HIP engine (reference: diagan-pkg/diagan/trainer/pr_score.py): pool-3 features of
 real images (cached as an npy, pr_score.py:44-72) and of generated images from the FID Inception-v3 network on the device, then
 diagan.trainer.compute_pr."""
-import os
 import time
 
-import numpy as np
 import torch
 
 from diagan.trainer import eval_common as E
@@ -18,20 +16,16 @@ def compute_real_features(num_samples, model, device, batch_size=50, dataset=Non
     """[num_samples, 2048] float32 numpy features of the first num_samples real images; loaded from feat_file when it exists,
     else computed and saved there.  Without feat_file a dataset NAME caches under log_dir/metrics/features; other datasets
     are not cached."""
-    tag = E.dataset_tag(dataset)
-    synthetic_cache = feat_file is None and tag is not None       # a cache this function computed from a dataset NAME
-    if synthetic_cache:
-        feat_dir = os.path.join(log_dir, 'metrics', 'features')
-        os.makedirs(feat_dir, exist_ok=True)
-        feat_file = os.path.join(feat_dir, "pr_feat_{}_{}k_run_{}.npy".format(tag, num_samples // 1000, seed))
-    elif feat_file is not None and not str(feat_file).endswith('.npy'):
-        feat_file = str(feat_file) + '.npy'
-    if feat_file and os.path.exists(feat_file):
+    feat_file, synthetic = E.real_cache_file(feat_file, dataset, log_dir, ('features',), "pr_feat_{}_{}k_run_{}.npy", num_samples,
+                                             seed)
+    feat_file = E.npy_file(feat_file)
+    feats = E.load_npy(feat_file)
+    if feats is not None:
         if verbose:
             print("INFO: Loading existing features for real images from {}...".format(feat_file))
-            if synthetic_cache:
-                print("WARNING: these features were computed from SYNTHETIC stand-in images of '{}'".format(tag))
-        return np.load(feat_file)
+            if synthetic:
+                print("WARNING: these features were computed from SYNTHETIC stand-in images of '{}'".format(dataset))
+        return feats
     if verbose:
         print("INFO: Computing features for real images...")
     feats = torch.cat(list(E.inception_batches(E.real_images(dataset, num_samples, batch_size), model, device, batch_size)))
@@ -39,8 +33,7 @@ def compute_real_features(num_samples, model, device, batch_size=50, dataset=Non
     if feat_file:
         if verbose:
             print("INFO: Saving features for real images to {}...".format(feat_file))
-        os.makedirs(os.path.dirname(os.path.abspath(feat_file)), exist_ok=True)
-        np.save(feat_file, feats)
+        E.save_npy(feat_file, feats)
     return feats
 
 
@@ -52,8 +45,7 @@ def pr_score(num_real_samples, num_fake_samples, netG, dataset, nearest_k=3, see
     model = E.resolve_model(model)
     E.seed_all(seed)
     real = compute_real_features(num_real_samples, model, device, batch_size, dataset, feat_file, seed, verbose, log_dir)
-    images = E.fake_images(netG, num_fake_samples, device, batch_size=batch_size, seed=seed, verbose=verbose)
-    fake = torch.cat(list(E.inception_batches(images, model, device, batch_size))).cpu().numpy()
+    fake = E.fake_features(netG, num_fake_samples, model, device, batch_size, seed, verbose).cpu().numpy()
     metrics = compute_pr(real_features=real, fake_features=fake, nearest_k=nearest_k, device=device)
     for key in metrics:
         print("INFO: {}: {} [Time Taken: {:.4f} secs]".format(key, metrics[key], time.time() - start_time))

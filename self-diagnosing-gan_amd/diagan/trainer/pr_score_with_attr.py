@@ -34,7 +34,7 @@ def partial_scores_with_attrs(attrs, num_real_samples, num_fake_samples, netG, d
         real = G.real_feature_bank(dataset, model, device, batch_size, feat_file, union, verbose)
     else:
         real = bank.index_select(0, torch.as_tensor(union).to(bank.device))
-    fake = G.fake_features(netG, num_fake_samples, model, device, batch_size, seed, verbose)
+    fake = E.fake_features(netG, num_fake_samples, model, device, batch_size, seed, verbose)
     flat = {(attr, side): np.searchsorted(union, idx) for attr, pair in groups.items()
             for side, idx in zip(('attr', 'not_attr'), pair)}
     scores = compute_group_prdc(real.cpu().numpy(), fake.cpu().numpy(), flat, nearest_k, device=device)
