@@ -25,7 +25,12 @@
  *   - RET is int, int64_t, size_t or const char*;
  *   - a parameter is an int, float, double, int64_t or long, or a pointer (of any depth, const or not) to one of those, to
  *     unsigned long long, to void, or to a struct declared here -- every pointer is bound as void*.
- * Anything else fails when the header is read, with the declaration's name (tests/test_native_abi.py).
+ * The records that cross the ABI are read from here too (diagan._native.records(): name -> aligned numpy dtype with the C field names),
+ * so a record has to stay in this form:
+ *   - `typedef struct [tag] { fields } diagan_name;`, each field line `TYPE declarator[, declarator ...];`;
+ *   - TYPE is int, int32_t, int64_t, float or double, or a pointer to anything (laid out as a uint64);
+ *   - a declarator is a name or a one-dimensional array `name[N]`; no nested structs, bit-fields or function pointers.
+ * Anything else fails when the header is read, with the declaration's or the record's name (tests/test_native_abi.py).
  */
 #ifndef DIAGAN_HIP_H
 #define DIAGAN_HIP_H
@@ -275,10 +280,7 @@ int diagan_conv_wino4_upin_supported(int B, int Hi, int Wi, int Ci, int Ho, int 
  * (tile_cfg 9, 11, 12, 13, 15) first transforms its weights into `splitk_ws` with a small kernel of its own: 48 (SNGAN-32) to
  * 124 (SNGAN-64) launches of 5-7 us per training step.  A caller that knows which layers it is about to run can instead
  *   1. transform the weights of MANY layers in one launch into buffers it owns: diagan_wino_weights_batched takes a device
- *      table of n { const float* w; float* u; int Co, Ci, Kp, kind, flip, blk0; float scale; int pad; } records (kind 2:
- *      F(2x2,3x3) format, used by tile_cfg 9 and the F(2x2) pooled launches; 40: F(4x4,3x3), tile_cfg 13 and -- with scale
- *      1/16 -- 15; 41: the 25-frequency format of tile_cfg 11 / 12 on the F(4x4) kernel; flip = 1 for a data gradient;
- *      blk0 = prefix sum of diagan_wino_weight_blocks(Co, Ci) over the table, `blocks` its total);
+ *      table of n diagan_wino_job records (below; `blocks`: the total of diagan_wino_weight_blocks(Co, Ci) over the table);
  *   2. tell the next diagan_conv_gemm call of this thread that its transformed weights are at `u` in that format
  *      (diagan_conv_gemm_weights_hint); the call uses them and skips its own transform if -- and only if -- the format is the
  *      one it needs, so a wrong guess costs nothing but the unused hint.
@@ -288,7 +290,18 @@ int diagan_conv_wino4_upin_supported(int B, int Hi, int Wi, int Ci, int Ho, int 
 int diagan_conv_gemm_weights_hint(const float* u, int kind, int flip, float scale);
 int diagan_conv_gemm_last_weight_format(int* kind, int* flip, float* scale, int64_t* floats, int64_t* launches);
 int64_t diagan_wino_weight_blocks(int Co, int Ci);
-int diagan_wino_weights_batched(const void* jobs, int n, int blocks, void* stream);
+typedef struct {
+  const float* w;    /* packed weights [Co][Kp] */
+  float* u;          /* transformed weights, in the format's own size */
+  int32_t Co, Ci, Kp;
+  int32_t kind;      /* 2: F(2x2,3x3) format, used by tile_cfg 9 and the F(2x2) pooled launches; 40: F(4x4,3x3), tile_cfg 13 and -- with
+                        scale 1/16 -- 15; 41: the 25-frequency format of tile_cfg 11 / 12 on the F(4x4) kernel */
+  int32_t flip;      /* 1 for a data gradient (taps reversed) */
+  int32_t blk0;      /* first workgroup of this job: prefix sum of diagan_wino_weight_blocks(Co, Ci) over the table */
+  float scale;
+  int32_t pad_;
+} diagan_wino_job;
+int diagan_wino_weights_batched(const diagan_wino_job* jobs, int n, int blocks, void* stream);
 int diagan_conv_gemm_pick_cfg_geom(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr,
                                    int off, int up, int Kp, int allow_split, int64_t ws_floats);
 /* The same choice for a launch with a GROUPED prologue (pro_group_rows > 0: one affine row per group of that many GEMM
@@ -377,7 +390,7 @@ typedef struct {
   int nctx, first_block; /* nctx: 1, or 2 when the backward covered two batched forwards; first_block: index of the
                             layer's first workgroup in the finish kernels' 1-D grid (prefix sum of ceil(n_elem/1024)) */
 } diagan_wgrad_layer;
-int diagan_wgrad_finish_batched(const void* table_dev, int n_layers, int64_t total_blocks, int any_sn, void* stream);
+int diagan_wgrad_finish_batched(const diagan_wgrad_layer* table_dev, int n_layers, int64_t total_blocks, int any_sn, void* stream);
 /* elements of a layer that one workgroup of the finish kernels handles, for a layer of `splits` splits per context: the host
  * lays out diagan_wgrad_layer::first_block (and sizes the <G, W> partial arrays) in units of it (1024 x {8, 4, 2, 1} for at most
  * 2, 4, 8 and more splits).  diagan_wgrad_layer::stride must be below 2^25 floats (the kernels address 16 splits of a layer through
@@ -415,11 +428,11 @@ typedef struct {
   float* Wd;         /* [Ci][Kd] data-gradient operand / sigma, or NULL */
   int Co, Ci, RS, Kp, Kd, pad;
 } diagan_sn_layer;
-int diagan_sn_prepare_batched(const void* table_dev, int n_layers, int max_Co, int max_Ci, int max_RS,
+int diagan_sn_prepare_batched(const diagan_sn_layer* table_dev, int n_layers, int max_Co, int max_Ci, int max_RS,
                               int max_Kp, float eps, int update_buffers, int write_wd, void* stream);
 /* write_wd: 1 pack Wf and Wd, 0 pack Wf only, -1 power iteration only.  diagan_pack_batched runs the
  * packing step alone (scale = state[1] of each descriptor). */
-int diagan_pack_batched(const void* table_dev, int n_layers, int max_Co, int max_Ci, int max_RS, int write_wd,
+int diagan_pack_batched(const diagan_sn_layer* table_dev, int n_layers, int max_Co, int max_Ci, int max_RS, int write_wd,
                         void* stream);
 
 /* GEMM operand packing: Wf = W*inv (same [Co][Kp] layout), Wd[ci][(rs)*Co+co] = W[co][(rs)*Ci+ci]*inv

@@ -6,10 +6,7 @@
 #include <stdarg.h>
 #include <mutex>
 
-#define DIAGAN_OK 0
-#define DIAGAN_EINVAL (-1)   // bad argument (shape / alignment / null pointer)
-#define DIAGAN_EHIP (-2)     // a HIP runtime call or kernel launch failed
-#define DIAGAN_EUNSUP (-3)   // configuration not supported by the kernels
+#include "diagan_hip.h"   // the C ABI: every prototype, record and DIAGAN_E* code the library defines is compiled against it
 
 #define DIAGAN_API extern "C" __attribute__((visibility("default")))
 

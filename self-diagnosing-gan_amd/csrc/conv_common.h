@@ -227,13 +227,8 @@ __device__ __forceinline__ bool wino_stage_taps(const float* __restrict__ w, int
 // split into three bf16 pieces per element, in the per-wave stream order of the X3 kernels (conv_wino4.hip).
 // 50 (round 5): not a Winograd format -- the packed GEMM operand split into three bf16 planes [piece][Co][Kp] (conv_gemm_x3.hip)
 enum WinoKind : int { WK_F2 = 2, WK_F4 = 40, WK_F4_POOL = 41, WK_F4X = 42, WK_F4X_POOL = 43, WK_GX3 = 50 };
-struct WinoJob {               // one layer of a batched transform (device table)
-  const float* w;              // packed weights [Co][Kp]
-  float* u;                    // transformed weights (format's own size: wino_ws_floats / wino4_ws_floats)
-  int Co, Ci, Kp, kind, flip, blk0;   // blk0: first workgroup of this job in the batched grid
-  float scale;
-  int pad_;
-};
+// (one layer of a batched transform is a diagan_wino_job of include/diagan_hip.h; its `u` has the format's own size: wino_ws_floats /
+//  wino4_ws_floats)
 // (conv_gemm.hip) the transformed weights this launch may use instead of transforming into `ws`: returns the hinted buffer if
 // the caller's hint matches the format, else nullptr; either way notes the format for diagan_conv_gemm_last_weight_format
 const float* wino_weights_ready(int kind, int flip, float scale, long floats);

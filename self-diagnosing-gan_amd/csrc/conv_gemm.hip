@@ -19,21 +19,11 @@
 //
 // Roofline: MFMA fp32 (algorithmic FLOP = 2*M*Co*K).
 #include "conv_common.h"
+#include "diagan_conv_x3.h"
 #include "switches.h"
 #include <type_traits>
 #include <stdlib.h>
 #include <string.h>
-
-extern "C" int diagan_conv_gemm_tile_rows(int cfg);
-extern "C" int diagan_conv_gemm_tile_cols(int cfg);
-extern "C" int diagan_conv_gemm_pick_ksplit(int M, int Co, int Kp, int cfg);
-extern "C" int diagan_conv_gemm_pick_cfg_geom(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy,
-                                              int dr, int off, int up, int Kp, int allow_split, int64_t ws_floats);
-extern "C" int diagan_conv_gemm_pick_cfg_grouped(int B, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy,
-                                                 int dr, int off, int up, int Kp, int allow_split, int64_t ws_floats,
-                                                 int pro_group_rows);
-extern "C" int diagan_conv_wino_supported(int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr,
-                                          int off, int up);
 
 namespace diagan {
 int launch_gemm_x3(const ConvGemmArgs& a, float* ws, bool resident, hipStream_t st);     // conv_gemm_x3.hip: bf16 pipe, exactly split operands
@@ -55,7 +45,7 @@ bool wino4_pool_ok(int B, int Ho, int Wo, int Ci, int Co, long ws_floats, bool f
 int launch_wino4_pool(ConvGemmArgs a, float* ws, hipStream_t st);
 int launch_wino4_unpool(ConvGemmArgs a, float* ws, hipStream_t st);
 bool wino4_upin_ok(int B, int Ho, int Wo, int Ci, int Co, long ws_floats, bool force);
-int launch_wino_weights_batched(const WinoJob* jobs, int n, int blocks, hipStream_t st);     // conv_wino4.hip (all formats)
+int launch_wino_weights_batched(const diagan_wino_job* jobs, int n, int blocks, hipStream_t st);     // conv_wino4.hip (all formats)
 int launch_wino4_upin(ConvGemmArgs a, float* ws, hipStream_t st);
 void wino4_set_x3(int mode);
 int wino4_get_x3();
@@ -891,9 +881,10 @@ DIAGAN_API int diagan_conv_gemm_last_weight_format(int* kind, int* flip, float* 
   return DIAGAN_OK;
 }
 DIAGAN_API int64_t diagan_wino_weight_blocks(int Co, int Ci) { return (int64_t)cdiv(Ci, 32) * cdiv(Co, 64); }
-DIAGAN_API int diagan_wino_weights_batched(const void* jobs, int n, int blocks, void* stream) {
+static_assert(sizeof(diagan_wino_job) == 48, "diagan_wino_job layout");
+DIAGAN_API int diagan_wino_weights_batched(const diagan_wino_job* jobs, int n, int blocks, void* stream) {
   DG_REQUIRE(jobs && n > 0 && blocks > 0, "wino_weights_batched: bad job table");
-  return launch_wino_weights_batched((const WinoJob*)jobs, n, blocks, (hipStream_t)stream);
+  return launch_wino_weights_batched(jobs, n, blocks, (hipStream_t)stream);
 }
 
 // see include/diagan_hip.h
@@ -1329,12 +1320,6 @@ DIAGAN_API int diagan_conv_gemm_set_splitk_tickets(int* buf, int64_t slots) {
   g_ticket_slots = (long)slots;
   return DIAGAN_OK;
 }
-struct diagan_conv_opts {     // mirrors the typedef of the same name in include/diagan_hip.h (56 bytes)
-  int32_t wino, wino4, wino4x, gemm_x3, gemm_x3b, splitk_fused, force_ksplit, tune;
-  int32_t* tickets;
-  int64_t ticket_slots;
-  int32_t gemm_x3_resident;
-};
 static_assert(sizeof(diagan_conv_opts) == 56, "diagan_conv_opts layout");
 // Selection options of the NEXT diagan_conv_gemm call of the calling thread (thread-local, consumed by that call whatever path it takes;
 // NULL clears a pending set).  See diagan_conv_opts in include/diagan_hip.h.

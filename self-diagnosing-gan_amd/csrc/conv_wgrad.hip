@@ -361,22 +361,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 // One descriptor per parameterised layer; blockIdx.z selects the layer.  A layer whose backward
 // covered two batched forwards (nctx == 2) has two slab halves, each with its own SN context; both
 // contributions are added by the same thread (no two writers per gradient element).
-struct WgFinish {          // mirrored by diagan_wgrad_layer in include/diagan_hip.h (120 bytes)
-  float* slab[2];          // [splits][stride] per context: weight partials (+ bias partials)
-  const float* u[2];       // SN: u', v, state of the forward each context belongs to
-  const float* v[2];
-  const float* state[2];
-  double* partials[2];     // SN: one fp64 partial of <G, W> per block of phase A, per context
-  float* grad;             // flat gradient region of the layer: weight [Co*Kp] then bias
-  const float* W;          // master weight (SN layers) or NULL
-  long stride;
-  int splits, n_elem, n_w, Kp;   // splits per context; n_elem = Co*Kp (+ Co if bias), n_w = Co*Kp
-  int nctx, first_block; // first_block: index of the layer's first workgroup in the 1-D grid of the finish kernels
-};
+// The descriptor is diagan_wgrad_layer of include/diagan_hip.h: n_elem = Co*Kp (+ Co if bias), n_w = Co*Kp; partials holds one fp64
+// partial of <G, W> per block of phase A, per context.
 
 // The finish kernels run on a 1-D grid with exactly ceil(n_elem / (1024 fin_u(splits))) workgroups per layer (a [blocks of the largest
 // layer] x [layers] grid launched 69 000 mostly empty workgroups for SNGAN-64 and spent its time dispatching them).
-__device__ __forceinline__ int find_layer(const WgFinish* __restrict__ tab, int n_layers, int bid) {
+__device__ __forceinline__ int find_layer(const diagan_wgrad_layer* __restrict__ tab, int n_layers, int bid) {
   int l = 0;
   while (l + 1 < n_layers && tab[l + 1].first_block <= bid) ++l;
   return l;
@@ -392,8 +382,8 @@ __device__ __forceinline__ T* uni(T* p) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
   return (T*)(((unsigned long)hi << 32) | lo);
 }
-__device__ __forceinline__ WgFinish load_uniform(const WgFinish* __restrict__ d) {
-  WgFinish L;
+__device__ __forceinline__ diagan_wgrad_layer load_uniform(const diagan_wgrad_layer* __restrict__ d) {
+  diagan_wgrad_layer L;
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     L.slab[c] = uni(d->slab[c]); L.u[c] = uni(d->u[c]); L.v[c] = uni(d->v[c]); L.state[c] = uni(d->state[c]);
@@ -417,7 +407,7 @@ __device__ __forceinline__ WgFinish load_uniform(const WgFinish* __restrict__ d)
 __host__ __device__ __forceinline__ int fin_u(int splits) { return splits <= 2 ? 8 : splits <= 4 ? 4 : splits <= 8 ? 2 : 1; }
 
 template <int U>
-__device__ __forceinline__ void fin_a(const WgFinish& L, int lb, double* red) {
+__device__ __forceinline__ void fin_a(const diagan_wgrad_layer& L, int lb, double* red) {
   constexpr int ELEMS = 1024 * U;
   constexpr int R = 16 / U;
   const bool sn = L.W != nullptr;
@@ -499,8 +489,8 @@ __device__ __forceinline__ void fin_dispatch(int U, F&& f) {
 
 // phase A: G_c = sum over the splits of context c (fixed order).  plain layers: grad += sum_c G_c.
 // SN layers: G_c kept in slab[c][0..] and the block's partial of <G_c, W> is written.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void wgrad_finish_a_kernel(const WgFinish* __restrict__ tab, int n_layers) {
-  const WgFinish L = load_uniform(tab + find_layer(tab, n_layers, blockIdx.x));
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void wgrad_finish_a_kernel(const diagan_wgrad_layer* __restrict__ tab, int n_layers) {
+  const diagan_wgrad_layer L = load_uniform(tab + find_layer(tab, n_layers, blockIdx.x));
   const int lb = blockIdx.x - L.first_block;          // workgroup index inside the layer
   const int U = fin_u(L.splits);
   if ((long)lb * 1024 * U >= L.n_elem) return;
@@ -510,8 +500,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
 // between A and B: <G_c, W> of every SN layer = sum of its phase-A partials, ONCE per layer (one workgroup each,
 // fixed reduction pattern: deterministic); stored behind the partials, at index nparts
-__global__ __launch_bounds__(256) void wgrad_finish_dot_kernel(const WgFinish* __restrict__ tab) {
-  const WgFinish L = tab[blockIdx.x];
+__global__ __launch_bounds__(256) void wgrad_finish_dot_kernel(const diagan_wgrad_layer* __restrict__ tab) {
+  const diagan_wgrad_layer L = tab[blockIdx.x];
   if (L.W == nullptr) return;
   __shared__ double red[256];
   const int fe = 1024 * fin_u(L.splits), nparts = (L.n_elem + fe - 1) / fe;
@@ -533,7 +523,7 @@ __global__ __launch_bounds__(256) void wgrad_finish_dot_kernel(const WgFinish* _
 // Branch-free like phase A: positions behind the layer, the bias part's u / v and the absent second context read zero through
 // out-of-range buffer offsets; two positions (ten 16-byte loads) per thread in flight at a time.
 template <int U>
-__device__ __forceinline__ void fin_b(const WgFinish& L, int lb) {
+__device__ __forceinline__ void fin_b(const diagan_wgrad_layer& L, int lb) {
   constexpr int ELEMS = 1024 * U;
   constexpr int UC = U > 1 ? 2 : 1;
   const int nparts = (L.n_elem + ELEMS - 1) / ELEMS;
@@ -591,8 +581,8 @@ __device__ __forceinline__ void fin_b(const WgFinish& L, int lb) {
   }
 }
 
-__global__ __launch_bounds__(256) void wgrad_finish_b_kernel(const WgFinish* __restrict__ tab, int n_layers) {
-  const WgFinish L = load_uniform(tab + find_layer(tab, n_layers, blockIdx.x));
+__global__ __launch_bounds__(256) void wgrad_finish_b_kernel(const diagan_wgrad_layer* __restrict__ tab, int n_layers) {
+  const diagan_wgrad_layer L = load_uniform(tab + find_layer(tab, n_layers, blockIdx.x));
   const int lb = blockIdx.x - L.first_block;
   const int U = fin_u(L.splits);
   if (L.W == nullptr || (long)lb * 1024 * U >= L.n_elem) return;
@@ -606,17 +596,11 @@ extern "C" __attribute__((visibility("default"))) int diagan_wgrad_finish_block_
 }  // namespace diagan
 
 using namespace diagan;
-extern "C" int diagan_conv_gemm_get_wino(void);
-extern "C" int diagan_conv_gemm_get_x3b(void);
-extern "C" int diagan_conv_wgrad_splits(int M, int Co, int Kp);
-extern "C" int diagan_conv_wgrad_uses_wino(int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int R, int S, int sy, int dr,
-                                           int off, int up, int Kp);
 
-DIAGAN_API int diagan_wgrad_finish_batched(const void* table_dev, int n_layers, int64_t total_blocks, int any_sn,
+DIAGAN_API int diagan_wgrad_finish_batched(const diagan_wgrad_layer* tab, int n_layers, int64_t total_blocks, int any_sn,
                                            void* stream) {
-  DG_REQUIRE(table_dev && n_layers > 0 && total_blocks > 0 && total_blocks < (1L << 31), "wgrad_finish_batched: bad args");
-  static_assert(sizeof(WgFinish) == 128, "descriptor layout");
-  const WgFinish* tab = (const WgFinish*)table_dev;
+  DG_REQUIRE(tab && n_layers > 0 && total_blocks > 0 && total_blocks < (1L << 31), "wgrad_finish_batched: bad args");
+  static_assert(sizeof(diagan_wgrad_layer) == 128, "descriptor layout");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(wgrad_finish_a_kernel, dim3((unsigned)total_blocks), dim3(256), 0, st, tab, n_layers);
   if (any_sn) {
@@ -727,15 +711,6 @@ DIAGAN_API int diagan_conv_wgrad(const float* dy, const float* x, float* slab, i
 }
 
 // see include/diagan_hip.h: the Winograd weight gradients of several layers (one prologue mode) in one launch
-struct diagan_wgrad_job {    // mirrors the typedef of the same name in include/diagan_hip.h (128 bytes)
-  const float* dy;
-  const float* x;
-  float* slab;
-  const float* pro_scale;
-  const float* pro_shift;
-  int64_t slab_stride, bias_off;
-  int32_t splits, segments, pro_mode, B, Hi, Wi, Ci, Ho, Wo, Co, R, S, sy, dr, off, up, Kp, pad_;
-};
 static_assert(sizeof(diagan_wgrad_job) == 128, "diagan_wgrad_job layout");
 // Which launches may share a batched launch: equal class = the same kernel template.  0: this layer launches on its own.
 //   100 + pro                         the Winograd F(3x3,2x2) weight gradient (conv_wgrad_wino.hip)

@@ -204,11 +204,11 @@ __global__ __launch_bounds__(512) void wino4x_weight_kernel(const float* __restr
 
 // the transforms of MANY layers in one launch (diagan_wino_weights_batched): workgroup -> job through the jobs' first-block
 // prefix (a handful of jobs: linear scan), then the job's own (channel block, column block) in the job's format
-__global__ __launch_bounds__(512) void wino_weights_batched_kernel(const WinoJob* __restrict__ jobs, int n) {
+__global__ __launch_bounds__(512) void wino_weights_batched_kernel(const diagan_wino_job* __restrict__ jobs, int n) {
   __shared__ f32x4 sg[WT_LDS_F4];
   int j = 0;
   while (j + 1 < n && (int)blockIdx.x >= jobs[j + 1].blk0) ++j;
-  const WinoJob job = jobs[j];
+  const diagan_wino_job job = jobs[j];
   const int lb = blockIdx.x - job.blk0, nbx = (job.Ci + 31) >> 5;
   if (job.kind == WK_GX3) gx3_weight_job(job.w, job.u, job.Co, job.Kp, lb, nbx * ((job.Co + 63) >> 6));
   else if (job.kind == WK_F4X) wino4x_weight_body<0>(job.w, job.u, job.Co, job.Ci, job.Kp, job.flip, job.scale, lb % nbx, lb / nbx, sg);
@@ -1365,7 +1365,7 @@ static const float* wino4_weights(const ConvGemmArgs& a, float* ws, int flip, fl
   return ws;
 }
 
-int launch_wino_weights_batched(const WinoJob* jobs, int n, int blocks, hipStream_t st) {
+int launch_wino_weights_batched(const diagan_wino_job* jobs, int n, int blocks, hipStream_t st) {
   hipLaunchKernelGGL(wino_weights_batched_kernel, dim3(blocks), dim3(512), 0, st, jobs, n);
   return check_launch("wino_weights_batched");
 }

@@ -325,27 +325,16 @@ DIAGAN_API int diagan_parity_weights(const float* w, float* buf, float* gw, int 
 // ================================================================================================
 namespace diagan {
 
-struct SnLayer {          // mirrored by diagan_sn_layer in include/diagan_hip.h (96 bytes)
-  const float* W;         // master weight [Co][Kp]
-  float* u_buf;           // module buffer sn_u [Co]
-  float* sigma_buf;       // module buffer sn_sigma [1]
-  float* u_out;           // [Co]  u' of this forward (kept for the backward)
-  float* v_out;           // [Kp]  v  of this forward
-  float* state;           // {sigma, 1/sigma}
-  float* work;            // [SN_RSPLIT*Kp + Co] scratch
-  float* Wf;              // [Co][Kp] scaled forward operand or NULL
-  float* Wd;              // [Ci][Kd] scaled data-gradient operand or NULL
-  int Co, Ci, RS, Kp, Kd, pad;
-};
+// (the descriptor is diagan_sn_layer of include/diagan_hip.h; its `work` holds SN_RSPLIT*Kp + Co floats)
 constexpr int SN_RSPLIT = 8;
 constexpr int SN_MAX_KP = 9216;
 
 // vpart[r][k] = sum_{n in row chunk r} u[n] W[n][k].  A workgroup covers 64 columns x one row chunk with 4 row lanes
 // (then an LDS reduction): 4x the workgroups of a one-thread-per-column mapping -- the large SNGAN-64 weights
 // (1024 x 4608) had 144 workgroups for 19 MB.
-__global__ __launch_bounds__(256) void sn_cols_batched_kernel(const SnLayer* __restrict__ tab) {
+__global__ __launch_bounds__(256) void sn_cols_batched_kernel(const diagan_sn_layer* __restrict__ tab) {
   __shared__ float red[4][64];
-  const SnLayer L = tab[blockIdx.z];
+  const diagan_sn_layer L = tab[blockIdx.z];
   const int kl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int k = blockIdx.x * 64 + kl;
   if (blockIdx.x * 64 >= L.Kp) return;
@@ -362,9 +351,9 @@ __global__ __launch_bounds__(256) void sn_cols_batched_kernel(const SnLayer* __r
 }
 
 // v_raw = sum_r vpart[r] (into LDS; block 0 also stores it to v_out); t_raw[n] = W[n] . v_raw, 8 rows/block
-__global__ __launch_bounds__(256) void sn_rows_batched_kernel(const SnLayer* __restrict__ tab) {
+__global__ __launch_bounds__(256) void sn_rows_batched_kernel(const diagan_sn_layer* __restrict__ tab) {
   __shared__ float vs[SN_MAX_KP];
-  const SnLayer L = tab[blockIdx.z];
+  const diagan_sn_layer L = tab[blockIdx.z];
   const int row0 = blockIdx.x * 8;
   if (row0 >= L.Co) return;
   for (int k = threadIdx.x; k < L.Kp; k += 256) {
@@ -390,10 +379,10 @@ __global__ __launch_bounds__(256) void sn_rows_batched_kernel(const SnLayer* __r
   }
 }
 
-__global__ __launch_bounds__(256) void sn_finalize_batched_kernel(const SnLayer* __restrict__ tab, float eps,
+__global__ __launch_bounds__(256) void sn_finalize_batched_kernel(const diagan_sn_layer* __restrict__ tab, float eps,
                                                                   int update_buffers) {
   __shared__ float red[4];
-  const SnLayer L = tab[blockIdx.z];
+  const diagan_sn_layer L = tab[blockIdx.z];
   const float* t_raw = L.work + (long)SN_RSPLIT * L.Kp;
   float s = 0.f;
   for (int k = threadIdx.x; k < L.Kp; k += 256) { const float v = L.v_out[k]; s += v * v; }
@@ -424,7 +413,7 @@ __global__ __launch_bounds__(256) void sn_finalize_batched_kernel(const SnLayer*
 // them empty, and spent its 60 us dispatching them (0.19 of the HBM rate on the bytes it moved).
 constexpr int PACK_MAX_LAYERS = 64;
 constexpr int PACK_GRID = 2048;
-__global__ __launch_bounds__(256) void pack_batched_kernel(const SnLayer* __restrict__ tab, int n_layers, int write_wd) {
+__global__ __launch_bounds__(256) void pack_batched_kernel(const diagan_sn_layer* __restrict__ tab, int n_layers, int write_wd) {
   __shared__ float tile[32][33];
   __shared__ int first[PACK_MAX_LAYERS + 1];
   if (threadIdx.x == 0) {
@@ -442,7 +431,7 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const SnLayer* __rest
   int l = 0;
   for (int item = blockIdx.x; item < total; item += gridDim.x) {
     while (first[l + 1] <= item) ++l;                          // items only grow: the search resumes where it stopped
-    const SnLayer L = tab[l];
+    const diagan_sn_layer L = tab[l];
     const int tc = (L.Ci + 31) / 32, tn = (L.Co + 31) / 32;
     int r = item - first[l];
     const int tap = r / (tc * tn);
@@ -471,15 +460,14 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const SnLayer* __rest
 
 }  // namespace diagan
 
-DIAGAN_API int diagan_sn_prepare_batched(const void* table_dev, int n_layers, int max_Co, int max_Ci, int max_RS,
+DIAGAN_API int diagan_sn_prepare_batched(const diagan_sn_layer* tab, int n_layers, int max_Co, int max_Ci, int max_RS,
                                          int max_Kp, float eps, int update_buffers, int write_wd, void* stream) {
-  DG_REQUIRE(table_dev && n_layers > 0 && max_Co > 0 && max_Ci > 0 && max_RS > 0 && max_Kp > 0,
+  DG_REQUIRE(tab && n_layers > 0 && max_Co > 0 && max_Ci > 0 && max_RS > 0 && max_Kp > 0,
              "sn_prepare_batched: bad args");
   DG_REQUIRE(max_Kp <= SN_MAX_KP, "sn_prepare_batched: Kp=%d exceeds the LDS-resident limit %d", max_Kp, SN_MAX_KP);
   DG_REQUIRE(n_layers <= PACK_MAX_LAYERS, "sn_prepare_batched: at most %d layers per table", PACK_MAX_LAYERS);
-  static_assert(sizeof(SnLayer) == 96, "descriptor layout");
+  static_assert(sizeof(diagan_sn_layer) == 96, "descriptor layout");
   hipStream_t st = (hipStream_t)stream;
-  const SnLayer* tab = (const SnLayer*)table_dev;
   hipLaunchKernelGGL(sn_cols_batched_kernel, dim3(cdiv(max_Kp, 64), SN_RSPLIT, n_layers), dim3(256), 0, st, tab);
   hipLaunchKernelGGL(sn_rows_batched_kernel, dim3(cdiv(max_Co, 8), 1, n_layers), dim3(256), 0, st, tab);
   hipLaunchKernelGGL(sn_finalize_batched_kernel, dim3(1, 1, n_layers), dim3(256), 0, st, tab, eps, update_buffers);
@@ -490,11 +478,10 @@ DIAGAN_API int diagan_sn_prepare_batched(const void* table_dev, int n_layers, in
 
 // Operand packing alone for a table of layers (scale = table state[1]; used with a unit-scale state to
 // produce the un-normalised data-gradient operand shared by two batched forwards).
-DIAGAN_API int diagan_pack_batched(const void* table_dev, int n_layers, int max_Co, int max_Ci, int max_RS,
+DIAGAN_API int diagan_pack_batched(const diagan_sn_layer* tab, int n_layers, int max_Co, int max_Ci, int max_RS,
                                    int write_wd, void* stream) {
-  DG_REQUIRE(table_dev && n_layers > 0 && max_Co > 0 && max_Ci > 0 && max_RS > 0, "pack_batched: bad args");
+  DG_REQUIRE(tab && n_layers > 0 && max_Co > 0 && max_Ci > 0 && max_RS > 0, "pack_batched: bad args");
   DG_REQUIRE(n_layers <= PACK_MAX_LAYERS, "pack_batched: at most %d layers per table", PACK_MAX_LAYERS);
-  hipLaunchKernelGGL(pack_batched_kernel, dim3(PACK_GRID), dim3(256), 0, (hipStream_t)stream, (const SnLayer*)table_dev,
-                     n_layers, write_wd);
+  hipLaunchKernelGGL(pack_batched_kernel, dim3(PACK_GRID), dim3(256), 0, (hipStream_t)stream, tab, n_layers, write_wd);
   return check_launch("pack_batched");
 }

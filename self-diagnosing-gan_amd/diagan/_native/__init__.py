@@ -54,19 +54,63 @@ def parse_header(text):
     return sigs
 
 
+_FIELDS = {"int": "i4", "int32_t": "i4", "int64_t": "i8", "float": "f4", "double": "f8"}
+
+
+def parse_records(text):
+    """name -> aligned numpy dtype (the C field names, a pointer as a uint64) of every `typedef struct [tag] { fields } name;` in the
+    text of a header; ValueError naming the record on a field outside the grammar the header's opening comment states."""
+    import numpy as np
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    recs = {}
+    for m in re.finditer(r"\btypedef\s+struct\s*\w*\s*\{", text):
+        end, depth = m.end(), 1
+        while depth and end < len(text):
+            depth += {"{": 1, "}": -1}.get(text[end], 0)
+            end += 1
+        tail = re.match(r"\s*(\w+)\s*;", text[end:])
+        if depth or not tail:
+            raise ValueError(f"typedef struct at offset {m.start()}: not a `typedef struct {{ fields }} name;` record")
+        name, fields = tail.group(1), []
+        for decl in filter(None, (d.strip() for d in text[m.end(): end - 1].split(";"))):
+            f = re.fullmatch(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(.*)", decl, flags=re.S)
+            typ, stars, names = (f.group(1), f.group(2), f.group(3).split(",")) if f else (None, "", [])
+            kind = "u8" if stars else _FIELDS.get(typ)
+            names = [re.fullmatch(r"\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", n) for n in names]
+            if kind is None or not all(names) or (stars and len(names) > 1):       # (`float* a, b` declares one pointer only)
+                raise ValueError(f"{name}: field '{' '.join(decl.split())}' is not one the binding knows")
+            fields += [(n.group(1), kind) if n.group(2) is None else (n.group(1), kind, (int(n.group(2)),)) for n in names]
+        recs[name] = np.dtype(fields, align=True)
+    return recs
+
+
+def _read(path):
+    if not os.path.exists(path):
+        raise RuntimeError(f"{os.path.basename(path)} not found at {path}: the ctypes signatures are read from it "
+                           "(the package runs from a checkout of the repository).")
+    with open(path) as f:
+        return f.read()
+
+
 _sigs = None
+_recs = None
 
 
 def signatures():
     """The table of the checkout's header, read once at first use."""
     global _sigs
     if _sigs is None:
-        if not os.path.exists(HEADER_PATH):
-            raise RuntimeError(f"diagan_hip.h not found at {HEADER_PATH}: the ctypes signatures are read from it "
-                               "(the package runs from a checkout of the repository).")
-        with open(HEADER_PATH) as f:
-            _sigs = parse_header(f.read())
+        _sigs = parse_header(_read(HEADER_PATH))
     return _sigs
+
+
+def records():
+    """The records of the checkout's header (parse_records), read once at first use."""
+    global _recs
+    if _recs is None:
+        _recs = parse_records(_read(HEADER_PATH))
+    return _recs
 
 
 def _bind(L, name):
@@ -140,3 +184,33 @@ def current_stream():
             torch.cuda.init()
             _raw_stream = lambda: get(cur())
     return _raw_stream()
+
+
+class Header:
+    """The binding of one of the small headers beside diagan_hip.h (`diagan._native.<name>_abi`): same library, same prototype
+    grammar and the same loud failures as this module, with a table of its own, read from `file_name` at first use.
+    signatures() here stays the table of diagan_hip.h alone."""
+
+    def __init__(self, file_name):
+        self.path = os.path.join(os.path.dirname(HEADER_PATH), file_name)
+        self._sigs, self._bound = None, {}
+
+    def signatures(self):
+        """name -> (restype, argtypes) of every prototype of the header, read once at first use."""
+        if self._sigs is None:
+            self._sigs = parse_header(_read(self.path))
+        return self._sigs
+
+    def fn(self, name):
+        f = self._bound.get(name)
+        if f is None:
+            f = getattr(lib(), name)
+            f.restype, f.argtypes = self.signatures()[name]
+            self._bound[name] = f
+        return f
+
+    def call(self, name, *args):
+        """Invoke an entry point; non-zero return -> RuntimeError with the library's message."""
+        rc = self.fn(name)(*args)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed ({rc}): {last_error()}")

@@ -4,40 +4,8 @@ Same library, same prototype grammar and the same loud failures as `diagan._nati
 header: `diagan._native.signatures()` stays the table of include/diagan_hip.h alone.  `diagan._native` does not import this module;
 the dataset code does (`from diagan._native import data_abi as dnat`).
 """
-import os
-
 from diagan import _native as nat
 from diagan._native import current_stream, parse_header, ptr  # noqa: F401  (re-exported for the call sites)
 
-HEADER_PATH = os.path.join(os.path.dirname(nat.HEADER_PATH), "diagan_data.h")
-
-_sigs = None
-_bound = {}
-
-
-def signatures():
-    """name -> (restype, argtypes) of every prototype of include/diagan_data.h, read once at first use."""
-    global _sigs
-    if _sigs is None:
-        if not os.path.exists(HEADER_PATH):
-            raise RuntimeError(f"diagan_data.h not found at {HEADER_PATH}: the ctypes signatures are read from it "
-                               "(the package runs from a checkout of the repository).")
-        with open(HEADER_PATH) as f:
-            _sigs = parse_header(f.read())
-    return _sigs
-
-
-def fn(name):
-    f = _bound.get(name)
-    if f is None:
-        f = getattr(nat.lib(), name)
-        f.restype, f.argtypes = signatures()[name]
-        _bound[name] = f
-    return f
-
-
-def call(name, *args):
-    """Invoke an entry point; non-zero return -> RuntimeError with the library's message."""
-    rc = fn(name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {nat.last_error()}")
+_header = nat.Header("diagan_data.h")
+HEADER_PATH, signatures, fn, call = _header.path, _header.signatures, _header.fn, _header.call

@@ -487,6 +487,42 @@ class HeadLinear(nn.Module):
         return gx
 
 
+def _sn_dims(m):
+    """Co, Ci, RS, Kp, Kd of a spectral-norm layer as the batched preparation sees it (HeadLinear: [1][C], used with inv_sigma only)"""
+    if isinstance(m, ConvLayer):
+        g = m.geom
+        return g.Co, g.Ci, g.R * g.S, g.Kp, g.Kd
+    return 1, m.in_ch, 1, m.in_ch, 0
+
+
+def sn_layer_table(layers, slot):
+    """the diagan_sn_layer table of context slot `slot` of the layers (SNBatch allocated the contexts)"""
+    import numpy as np
+    from diagan import _native as nat
+    tab = np.zeros(len(layers), dtype=nat.records()["diagan_sn_layer"])
+    for row, m in zip(tab, layers):
+        ctx = m._slot_ctx[slot]
+        row['W'], row['u_buf'], row['sigma_buf'] = m.weight.data.data_ptr(), m.sn_u.data_ptr(), m.sn_sigma.data_ptr()
+        row['u_out'], row['v_out'], row['state'] = ctx.u.data_ptr(), ctx.v.data_ptr(), ctx.state.data_ptr()
+        row['work'] = ctx._keep[0].data_ptr()
+        if isinstance(m, ConvLayer):
+            row['Wf'], row['Wd'] = ctx.wf.data_ptr(), ctx.wd.data_ptr()
+        row['Co'], row['Ci'], row['RS'], row['Kp'], row['Kd'] = _sn_dims(m)
+    return tab
+
+
+def sn_pair_table(convs, unit):
+    """the diagan_sn_layer table of diagan_pack_batched for the pair mode: the un-normalised data-gradient operand of every
+    convolution (its _pair_ctx.wd) from the master weight, scale = unit[1]"""
+    import numpy as np
+    from diagan import _native as nat
+    tab = np.zeros(len(convs), dtype=nat.records()["diagan_sn_layer"])
+    for row, m in zip(tab, convs):
+        row['W'], row['state'], row['Wd'] = m.weight.data.data_ptr(), unit.data_ptr(), m._pair_ctx.wd.data_ptr()
+        row['Co'], row['Ci'], row['RS'], row['Kp'], row['Kd'] = _sn_dims(m)
+    return tab
+
+
 class SNBatch:
     """All spectral-norm layers of one network prepared in 4 launches (diagan_sn_prepare_batched).
 
@@ -494,50 +530,33 @@ class SNBatch:
     forward's (u, v, sigma, Wf, Wd) must survive until that forward's backward."""
 
     def __init__(self, net, layers, n_slots=2):
-        import numpy as np
         from diagan import _native as nat
         self.net, self.layers, self.nat = net, layers, nat
         dev = net.flat_params.device
         self.slab_generation = net.slab_generation
-        desc = np.dtype([('p', np.uint64, 9), ('i', np.int32, 6)])
         self.tables = []
         f32 = dict(dtype=torch.float32, device=dev)
-        dims = []
         for slot in range(n_slots):
-            tab = np.zeros(len(layers), dtype=desc)
-            for li, m in enumerate(layers):
+            for m in layers:
+                Co, Ci, RS, Kp, Kd = _sn_dims(m)
                 if isinstance(m, ConvLayer):
-                    g = m.geom
-                    Co, Ci, RS, Kp, Kd = g.Co, g.Ci, g.R * g.S, g.Kp, g.Kd
-                    wf, wd = torch.zeros((Co, Kp), **f32), torch.zeros((Ci, Kd), **f32)
                     ctx = ConvLayer.Ctx()
-                else:                                   # HeadLinear: [1][C], used with inv_sigma only
-                    Co, Ci, RS, Kp, Kd = 1, m.in_ch, 1, m.in_ch, 0
-                    wf = wd = None
+                    ctx.wf, ctx.wd, ctx.wkey = torch.zeros((Co, Kp), **f32), torch.zeros((Ci, Kd), **f32), slot
+                else:
                     ctx = HeadLinear.Ctx()
                 ctx.u, ctx.v, ctx.state = torch.zeros(Co, **f32), torch.zeros(Kp, **f32), torch.ones(2, **f32)
-                if isinstance(m, ConvLayer):
-                    ctx.wf, ctx.wd, ctx.wkey = wf, wd, slot
-                work = torch.zeros(8 * Kp + Co, **f32)
-                ctx._keep = (work,)
+                ctx._keep = (torch.zeros(8 * Kp + Co, **f32),)             # the preparation's work buffer
                 if not hasattr(m, '_slot_ctx') or m._slot_ctx is None or len(m._slot_ctx) != n_slots:
                     m._slot_ctx = [None] * n_slots
                 m._slot_ctx[slot] = ctx
-                ptrs = [m.weight.data.data_ptr(), m.sn_u.data_ptr(), m.sn_sigma.data_ptr(), ctx.u.data_ptr(),
-                        ctx.v.data_ptr(), ctx.state.data_ptr(), work.data_ptr(),
-                        wf.data_ptr() if wf is not None else 0, wd.data_ptr() if wd is not None else 0]
-                tab[li]['p'] = ptrs
-                tab[li]['i'] = [Co, Ci, RS, Kp, Kd, 0]
-                dims.append((Co, Ci, RS, Kp))
-            self.tables.append(torch.from_numpy(tab.view(np.uint8).copy()).to(dev))
-        self.max = [max(d[k] for d in dims) for k in range(4)]
+            self.tables.append(C.upload_table(sn_layer_table(layers, slot), dev))
+        self.max = [max(_sn_dims(m)[k] for m in layers) for k in range(4)]
         # "pair" mode: two forwards (different sigma) batched into one GEMM on the UN-normalised weight:
         # forward operand = master weight, data-gradient operand = un-normalised transpose pack (made
         # once per parameter update), per-forward 1/sigma applied in the GEMM epilogue.
         convs = [m for m in layers if isinstance(m, ConvLayer)]
         self.unit = torch.ones(2, **f32)
-        ptab = np.zeros(len(convs), dtype=desc)
-        for li, m in enumerate(convs):
+        for m in convs:
             g = m.geom
             wd_raw = torch.zeros((g.Ci, g.Kd), **f32)
             pc = ConvLayer.Ctx()
@@ -547,9 +566,7 @@ class SNBatch:
             pc.pair = (m._slot_ctx[0], m._slot_ctx[1])
             pc.wkey = 'pair'
             m._pair_ctx = pc
-            ptab[li]['p'] = [m.weight.data.data_ptr(), 0, 0, 0, 0, self.unit.data_ptr(), 0, 0, wd_raw.data_ptr()]
-            ptab[li]['i'] = [g.Co, g.Ci, g.R * g.S, g.Kp, g.Kd, 0]
-        self.pair_table = torch.from_numpy(ptab.view(np.uint8).copy()).to(dev)
+        self.pair_table = C.upload_table(sn_pair_table(convs, self.unit), dev)
         self.n_convs = len(convs)
         self.pair_version = None
         self.convs = convs
@@ -607,6 +624,36 @@ class WgradEntry:
             self.splits = splits
             self.slab = torch.empty(splits * self.stride, dtype=torch.float32, device=self.slab.device)
             self.owner.drop_tables(self.slot)
+
+
+def wgrad_layer_table(layer_entries):
+    """(diagan_wgrad_layer table of [(layer, its WgradEntry)], total workgroups of the finish kernels, whether a layer has SN)"""
+    import numpy as np
+    from diagan import _native as nat
+    tab = np.zeros(len(layer_entries), dtype=nat.records()["diagan_wgrad_layer"])
+    any_sn, total_blocks = 0, 0
+    for row, (layer, e) in zip(tab, layer_entries):
+        c = e.sn_ctx
+        ctxs = list(c) if isinstance(c, tuple) else [c]
+        nctx = len(ctxs)
+        per = e.splits // nctx                  # splits of each batched forward
+        sn = ctxs[0] is not None
+        any_sn |= int(sn)
+        for pi, cc in enumerate(ctxs):
+            row['slab'][pi] = e.slab.data_ptr() + 4 * pi * per * e.stride
+            if sn:
+                row['u'][pi], row['v'][pi], row['state'][pi] = cc.u.data_ptr(), cc.v.data_ptr(), cc.state.data_ptr()
+            row['partials'][pi] = e.partials[pi].data_ptr()
+        if not sn and nctx > 1:                    # plain layer: one context over all splits
+            nctx, per = 1, e.splits
+        row['grad'] = layer.weight.grad.data_ptr()
+        row['W'] = layer.weight.data.data_ptr() if sn else 0
+        assert 64 * e.stride < 2 ** 31, "wgrad finish: 16 splits of a layer must fit a 2 GiB buffer window"
+        row['stride'], row['splits'], row['n_elem'], row['n_w'], row['Kp'] = e.stride, per, e.n_elem, e.n_w, layer.geom.Kp
+        row['nctx'], row['first_block'] = nctx, total_blocks
+        be = nat.fn("diagan_wgrad_finish_block_elems")(per)          # elements per workgroup of the finish kernels
+        total_blocks += (e.n_elem + be - 1) // be
+    return tab, total_blocks, any_sn
 
 
 class WgradBatch:
@@ -753,41 +800,14 @@ class WgradBatch:
         return layers[:h], layers[h:], cut
 
     def _finish_layers(self, slot, layers):
-        import numpy as np
         from diagan import _native as nat
         if not layers:
             return
         key = (slot, tuple(id(l) for l in layers))
         t = self.tables.get(key)
         if t is None:
-            desc = np.dtype([('p', np.uint64, 12), ('stride', np.int64), ('i', np.int32, 6)])
-            tab = np.zeros(len(layers), dtype=desc)
-            any_sn, total_blocks = 0, 0
-            for li, layer in enumerate(layers):
-                e = self.entries[(layer, slot)]
-                c = e.sn_ctx
-                ctxs = list(c) if isinstance(c, tuple) else [c]
-                nctx = len(ctxs)
-                per = e.splits // nctx                  # splits of each batched forward
-                sn = ctxs[0] is not None
-                any_sn |= int(sn)
-                pp = [0] * 12
-                for pi, cc in enumerate(ctxs):
-                    pp[0 + pi] = e.slab.data_ptr() + 4 * pi * per * e.stride
-                    if sn:
-                        pp[2 + pi], pp[4 + pi], pp[6 + pi] = cc.u.data_ptr(), cc.v.data_ptr(), cc.state.data_ptr()
-                    pp[8 + pi] = e.partials[pi].data_ptr()
-                if not sn and nctx > 1:                    # plain layer: one context over all splits
-                    nctx, per = 1, e.splits
-                pp[10] = layer.weight.grad.data_ptr()
-                pp[11] = layer.weight.data.data_ptr() if sn else 0
-                assert 64 * e.stride < 2 ** 31, "wgrad finish: 16 splits of a layer must fit a 2 GiB buffer window"
-                tab[li]['p'], tab[li]['stride'] = pp, e.stride
-                tab[li]['i'] = [per, e.n_elem, e.n_w, layer.geom.Kp, nctx, total_blocks]
-                be = nat.fn("diagan_wgrad_finish_block_elems")(per)          # elements per workgroup of the finish kernels
-                total_blocks += (e.n_elem + be - 1) // be
-            t = (torch.from_numpy(tab.view(np.uint8).copy()).to(layers[0].weight.device), len(layers), total_blocks, any_sn)
-            self.tables[key] = t
+            tab, total_blocks, any_sn = wgrad_layer_table([(layer, self.entries[(layer, slot)]) for layer in layers])
+            t = self.tables[key] = (C.upload_table(tab, layers[0].weight.device), len(layers), total_blocks, any_sn)
         nat.call("diagan_wgrad_finish_batched", t[0].data_ptr(), t[1], t[2], t[3], nat.current_stream())
 
 

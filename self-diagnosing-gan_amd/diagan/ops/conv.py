@@ -140,28 +140,39 @@ class WinoWeightBatch:
         Called at the start of the pass, after the operands the sites read have been written."""
         if not WINO_BATCH:
             return
-        import numpy as np
         todo = [s for s in self.sites if s.fmt is not None and s.fmt[0] and s.used and s.ready != version]
         if not todo:
             return
         key = tuple((id(s), s.fmt, s.w_of().data_ptr()) for s in todo)
         if key != self._table_key:
-            desc = np.dtype([('w', np.uint64), ('u', np.uint64), ('i', np.int32, 6), ('scale', np.float32), ('pad', np.int32)])
-            tab, blk = np.zeros(len(todo), dtype=desc), 0
-            for j, s in enumerate(todo):
-                w = s.w_of()
-                if s.u is None or s.u.numel() != s.fmt[3] or s.u.device != w.device:
-                    s.u = torch.empty(s.fmt[3], dtype=torch.float32, device=w.device)
-                tab[j]['w'], tab[j]['u'] = w.data_ptr(), s.u.data_ptr()
-                tab[j]['i'] = [s.Co, s.Ci, s.Kp, s.fmt[0], s.fmt[1], blk]
-                tab[j]['scale'] = s.fmt[2]
-                blk += nat.fn("diagan_wino_weight_blocks")(s.Co, s.Ci)
-            dev_tab = torch.from_numpy(tab.view(np.uint8).copy()).to(todo[0].w_of().device)
-            self._table_key, self._tables = key, (dev_tab, len(todo), blk)
+            tab, blk = wino_job_table(todo)
+            self._table_key, self._tables = key, (upload_table(tab, todo[0].w_of().device), len(todo), blk)
         tab, n, blocks = self._tables
         nat.call("diagan_wino_weights_batched", nat.ptr(tab), n, blocks, nat.current_stream())
         for s in todo:
             s.ready = version
+
+
+def wino_job_table(sites):
+    """(diagan_wino_job table of the sites, total workgroups): every site's transform buffer `u` is (re)allocated to its format's size"""
+    import numpy as np
+    tab, blk = np.zeros(len(sites), dtype=nat.records()["diagan_wino_job"]), 0
+    for row, s in zip(tab, sites):
+        w = s.w_of()
+        if s.u is None or s.u.numel() != s.fmt[3] or s.u.device != w.device:
+            s.u = torch.empty(s.fmt[3], dtype=torch.float32, device=w.device)
+        row['w'], row['u'] = w.data_ptr(), s.u.data_ptr()
+        row['Co'], row['Ci'], row['Kp'] = s.Co, s.Ci, s.Kp
+        row['kind'], row['flip'], row['scale'] = s.fmt[:3]
+        row['blk0'] = blk
+        blk += nat.fn("diagan_wino_weight_blocks")(s.Co, s.Ci)
+    return tab, blk
+
+
+def upload_table(tab, device):
+    """a numpy record table as a byte tensor on `device`"""
+    import numpy as np
+    return torch.from_numpy(tab.view(np.uint8).copy()).to(device)
 
 
 def _hint(wsite, version):
@@ -322,20 +333,28 @@ def set_splitk_fused(on):
 class ConvOpts(_ct.Structure):
     """diagan_conv_opts (include/diagan_hip.h): the selection options of ONE call -- `with conv_opts(wino=0): conv_fwd(...)` hands them
     to the next diagan_conv_gemm call of this thread; nothing process-wide is touched"""
-    _fields_ = [(n, _ct.c_int32) for n in ("wino", "wino4", "wino4x", "gemm_x3", "gemm_x3b", "splitk_fused", "force_ksplit", "tune")] + \
-               [("tickets", _ct.c_void_p), ("ticket_slots", _ct.c_int64), ("gemm_x3_resident", _ct.c_int32)]
+    _fields_ = [(n, {"u8": _ct.c_void_p, "i4": _ct.c_int32, "i8": _ct.c_int64}[t.str[1:]])
+                for n, (t, _) in nat.records()["diagan_conv_opts"].fields.items()]
+
+
+_OPTS_DEFAULT = dict(force_ksplit=0, tickets=None, ticket_slots=0)       # every other field: -1
+
+
+def make_opts(tickets=None, **fields):
+    """a ConvOpts with every field at its default but `fields` (and the ticket buffer `tickets`): what next_opts hands over"""
+    o = ConvOpts(**{n: _OPTS_DEFAULT.get(n, -1) for n, _ in ConvOpts._fields_})
+    for k, v in fields.items():
+        setattr(o, k, int(v))
+    if tickets is not None:
+        o.tickets, o.ticket_slots = tickets.data_ptr(), tickets.numel()
+    return o
 
 
 def next_opts(tickets=None, **fields):
     """options of the next convolution launch of this thread: wino / wino4 / wino4x / gemm_x3 / gemm_x3b / splitk_fused /
     gemm_x3_resident (-1 default, 0, 1), force_ksplit (0 = policy), tune (-1 default); tickets: a zeroed int32 CUDA tensor for the
     in-kernel split-K combine"""
-    o = ConvOpts(-1, -1, -1, -1, -1, -1, 0, -1, None, 0, -1)
-    for k, v in fields.items():
-        setattr(o, k, int(v))
-    if tickets is not None:
-        o.tickets, o.ticket_slots = tickets.data_ptr(), tickets.numel()
-    nat.call("diagan_conv_gemm_next_opts", _ct.byref(o))
+    nat.call("diagan_conv_gemm_next_opts", _ct.byref(make_opts(tickets, **fields)))
 
 
 def pending_opts():
@@ -346,7 +365,7 @@ def pending_opts():
 
 
 def _opts_key(o):
-    return tuple(getattr(o, n) for n, _ in ConvOpts._fields_[:8]) + (o.gemm_x3_resident,)
+    return (o.wino, o.wino4, o.wino4x, o.gemm_x3, o.gemm_x3b, o.splitk_fused, o.force_ksplit, o.tune, o.gemm_x3_resident)
 
 
 def _without_wino(o):
@@ -800,7 +819,42 @@ def wgrad_launch_plan(shapes):
     return plan
 
 
-_WG_JOB = None
+_WG_GEO = ("B", "Hi", "Wi", "Ci", "Ho", "Wo", "Co", "R", "S", "sy", "dr", "off", "up", "Kp")     # the ABI's geometry list, by field
+
+
+def wgrad_job_table(jobs):
+    """(diagan_wgrad_job table of [WgradJob] with its constant columns filled, its (n, 5) uint64 view of the five pointer columns
+    dy, x, slab, pro_scale, pro_shift -- what wgrad_job_ptrs gives --, FLOP, pixels, prologue mode of the launch)"""
+    import numpy as np
+    rec = nat.records()["diagan_wgrad_job"]
+    assert [(rec.fields[n][0].str[1:], rec.fields[n][1]) for n in ("dy", "x", "slab", "pro_scale", "pro_shift")] == \
+        [("u8", 8 * k) for k in range(5)] and rec.itemsize % 8 == 0
+    tab = np.zeros(len(jobs), dtype=rec)
+    flop, px, mode0 = 0.0, 0, None
+    for row, job in zip(tab, jobs):
+        e, s = job.entry, job.shape
+        geo = _wgrad_geo(s.geom, s.dy_shape, s.x_shape)
+        B, Hi, Wi, Ci, Ho, Wo, Co, R, S = geo[:9]
+        mode = _pro3(job.pro)[0]
+        mode0 = mode if mode0 is None else mode0
+        row['slab_stride'], row['bias_off'] = e.stride, e.bias_off
+        row['splits'], row['segments'], row['pro_mode'] = e.splits, s.segments, mode
+        for n, v in zip(_WG_GEO, geo):
+            row[n] = v
+        flop += 2.0 * B * Ho * Wo * Co * R * S * Ci
+        px += B * Ho * Wo
+    return tab, tab.view(np.uint64).reshape(len(jobs), -1)[:, :5], flop, px, mode0
+
+
+def wgrad_job_ptrs(jobs):
+    """the five pointers of every job, in the order of the record's first five fields"""
+    ptrs = []
+    for job in jobs:
+        pro = job.pro
+        scale, shift = (pro[1], pro[2]) if pro is not None and len(pro) > 2 else (None, None)
+        ptrs.append((job.dy.data_ptr(), job.x.data_ptr(), job.entry.slab.data_ptr(), 0 if scale is None else scale.data_ptr(),
+                     0 if shift is None else shift.data_ptr()))
+    return ptrs
 
 
 def conv_wgrad_batched(jobs, kernel_name, flop_scale=1.0, key=None, cache=None):
@@ -809,38 +863,15 @@ def conv_wgrad_batched(jobs, kernel_name, flop_scale=1.0, key=None, cache=None):
     key, cache: a hashable that identifies everything but the tensors' addresses (layers, shapes, splits) and the caller's table
     cache: the job table's constant columns are built once and only the five pointers per job are refreshed (host time matters
     on launch-bound nets).  WgradBatch keeps one cache per network: it dies with the net, so no id in `key` is recycled."""
-    global _WG_JOB
-    import numpy as np
-    if _WG_JOB is None:
-        _WG_JOB = np.dtype([('p', np.uint64, 5), ('l', np.int64, 2), ('i', np.int32, 18)])
-        assert _WG_JOB.itemsize == 128
     cached = cache.get(key) if cache is not None else None
     if cached is None:
-        tab = np.zeros(len(jobs), dtype=_WG_JOB)
-        flop, px, mode0 = 0.0, 0, None
-        for j, job in enumerate(jobs):
-            e, s = job.entry, job.shape
-            geo = _wgrad_geo(s.geom, s.dy_shape, s.x_shape)
-            B, Hi, Wi, Ci, Ho, Wo, Co, R, S = geo[:9]
-            mode = _pro3(job.pro)[0]
-            mode0 = mode if mode0 is None else mode0
-            tab[j]['l'] = [e.stride, e.bias_off]
-            tab[j]['i'] = [e.splits, s.segments, mode, *geo, 0]
-            flop += 2.0 * B * Ho * Wo * Co * R * S * Ci
-            px += B * Ho * Wo
-        cached = (tab, flop, px, mode0)
+        cached = wgrad_job_table(jobs)
         if cache is not None:
             if len(cache) > 256:
                 cache.clear()
             cache[key] = cached
-    tab, flop, px, mode0 = cached
-    ptrs = []
-    for job in jobs:
-        pro = job.pro
-        scale, shift = (pro[1], pro[2]) if pro is not None and len(pro) > 2 else (None, None)
-        ptrs.append((job.dy.data_ptr(), job.x.data_ptr(), job.entry.slab.data_ptr(), 0 if scale is None else scale.data_ptr(),
-                     0 if shift is None else shift.data_ptr()))
-    tab['p'] = ptrs
+    tab, tab_ptrs, flop, px, mode0 = cached
+    tab_ptrs[...] = wgrad_job_ptrs(jobs)
     timed = TIMER is not None and TIMER.wants_any()
     t0 = TIMER.begin(kernel_name) if timed else None
     nat.call("diagan_conv_wgrad_batched", tab.ctypes.data, len(jobs), nat.current_stream())
