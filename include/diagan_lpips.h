@@ -10,7 +10,8 @@
  * the text in diagan_last_error(), launch on `stream`, no synchronisation, no allocation.  Every output element is formed by one
  * thread or one workgroup in an order fixed by the image's shape alone (no atomics, nothing depends on B): reruns are
  * bit-identical and an image's value does not depend on the batch it is in.
- * Every name here starts with diagan_lpips_ and returns int, except the workspace query.
+ * Every name of this part starts with diagan_lpips_ and returns int, except the workspace query.  The head of the attribute
+ * classifier, which runs on the same VGG16 feature extractor, follows at the end of the file (diagan_attr_*).
  */
 #ifndef DIAGAN_LPIPS_H
 #define DIAGAN_LPIPS_H
@@ -60,6 +61,63 @@ size_t diagan_lpips_head_ws_bytes(int B, int H, int W, int C);
  * image_stride a multiple of 4; ws 8-byte aligned with ws_bytes >= diagan_lpips_head_ws_bytes(B, H, W, C). */
 int diagan_lpips_head(const float* f0, const float* f1, int64_t image_stride, int B, int H, int W, int C, const float* w,
                       double* out, int add, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- the head of the CelebA attribute classifier, a VGG16 with a two-class last layer ------------------
+ *
+ * The classifier's 13 convolutions run on diagan_incep_conv and its five max pools on diagan_lpips_pool2 above; the entry points
+ * below add what its head needs: AdaptiveAvgPool2d((7, 7)) with the flatten, a dense layer wider than one output with its data
+ * gradient and a weight gradient that carries the SGD step, the softmax cross-entropy and the count of the rows that show the
+ * attribute.  They are declared in this header because it is the one diagan/_native/lpips_abi.py binds: the VGG16 family shares
+ * one table.  Same conventions as above.  All tensors are fp32, row-major and contiguous unless stated.  No atomics: every
+ * output element is formed by one thread or one workgroup in an order fixed by the shapes alone, so reruns are bit-identical; in
+ * the forward pass a row's values do not depend on the other rows of the batch.  Every name starts with diagan_attr_ and returns int.
+ *
+ * A dense layer here is  Y[M][N] = act(X[M][K] W[N][K]^T + b[N]) * keep,  act = ReLU or nothing, keep = mask * drop_scale with
+ * the 0 / 1 mask as bernoulli_ wrote it and drop_scale = 1 / (1 - p) (the convention of diagan_act_fwd), or 1 without a mask.
+ * The gradient with respect to the pre-activation is  dZ = dY * [Y > 0] * keep  ([Y > 0] only for a ReLU layer, where the caller
+ * passes Y; keep only where the caller passes the mask); the data gradient and the weight gradient form dZ while they load dY.
+ */
+
+/* nn.AdaptiveAvgPool2d((7, 7)) and the flatten, from NHWC: x [B][H][W][C] -> y [B][C 49] with y[b][c 49 + i 7 + j] the mean of
+ * rows floor(i H / 7) .. ceil((i + 1) H / 7) - 1 and the same columns in j and W: torchvision's order.  The sum runs row by row
+ * in fp32 and is divided by the bin's size once.  H, W in [1, 2^20]. */
+int diagan_attr_pool_flatten(const float* x, int B, int H, int W, int C, float* y, void* stream);
+
+/* The dense layer of the comment above.  bias may be NULL (none); relu != 0 applies ReLU; mask NULL means keep = 1.
+ * N <= 4 takes a path of its own (a wave per row, N dot products); wider layers run on v_mfma_f32_16x16x4_f32 with exact fp32
+ * products: a workgroup owns 16 columns and every row (128 rows per grid row for M > 128), its eight waves split K and add their
+ * parts in wave order, so W is read from memory once.  K, N, M >= 1; 16-byte loads when K is a multiple of 4 and x and w are
+ * 16-byte aligned, scalar loads otherwise. */
+int diagan_attr_dense_fwd(const float* x, const float* w, const float* bias, int M, int K, int N, int relu, const float* mask,
+                          float drop_scale, float* y, void* stream);
+
+/* dX[M][K] = dZ[M][N] W[N][K],  dZ from dy [M][N] as above: y (the layer's output, NULL for a layer without ReLU), mask (NULL
+ * for none) and drop_scale.  A workgroup owns 32 columns of K and every row; its four waves split N. */
+int diagan_attr_dense_dgrad(const float* dy, const float* y, const float* mask, float drop_scale, const float* w, int M, int K,
+                            int N, float* dx, void* stream);
+
+/* The weight gradient and the optimiser step in one launch, M <= 128:
+ *   g[n][k] = sum_m dZ[m][n] x[m][k],   buf_w = momentum buf_w + g,   w -= lr buf_w,
+ * and the same for the bias with g[n] = sum_m dZ[m][n] (bias, buf_b NULL: a layer without bias).  With zero-initialised buffers
+ * this is torch.optim.SGD(lr, momentum) with dampening 0, no Nesterov step and no weight decay.  The sum over the batch runs
+ * in row order inside one wave; the gradient never reaches memory.  w is updated in place: launch it after the layer's data
+ * gradient has read w.
+ * g_w != NULL (with g_b, or g_b NULL to skip the bias) writes g there instead and leaves w, bias and the buffers alone: for tests. */
+int diagan_attr_dense_wgrad_sgd(const float* dy, const float* y, const float* mask, float drop_scale, const float* x, int M, int K,
+                                int N, float lr, float momentum, float* w, float* bias, float* buf_w, float* buf_b, float* g_w,
+                                float* g_b, void* stream);
+
+/* Softmax cross-entropy with mean reduction: logits [M][N], 1 <= N <= 64, targets int64 [M] in [0, N).
+ *   dlogit[m][n] = (softmax(logits[m])[n] - [n == target[m]]) / M                       (fp32, computed in float64)
+ *   loss_acc[0]    += 1 / M sum_m (log sum_n exp(z[m][n] - max_n z[m]) - (z[m][t] - max_n z[m]))      (float64 from the load on)
+ *   correct_acc[0] += the number of rows whose FIRST maximum is at the target (torch.max(output, 1))
+ * One workgroup; the accumulators are read and written by one thread, so successive launches on a stream add up. */
+int diagan_attr_ce(const float* logits, const int64_t* target, int M, int N, float* dlogit, double* loss_acc,
+                   int64_t* correct_acc, void* stream);
+
+/* counter[0] += the number of rows of logits [M][N] whose first maximum is not at column 0 (a tie with column 0 counts as
+ * class 0).  1 <= N <= 64.  One workgroup, as diagan_attr_ce. */
+int diagan_attr_count(const float* logits, int M, int N, int64_t* counter, void* stream);
 
 #ifdef __cplusplus
 }

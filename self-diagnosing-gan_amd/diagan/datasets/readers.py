@@ -241,6 +241,45 @@ def read_celeba(root, size=64, resize=None, workers=None, **unused):
     return images, targets
 
 
+CELEBA_SPLITS = {'train': '0', 'valid': '1', 'test': '2'}          # the partitions of list_eval_partition.txt
+
+
+def celeba_split_files(root, split):
+    """file names of a split (`train` / `valid` / `test`: partition 0 / 1 / 2) in the order of list_eval_partition.txt"""
+    if split not in CELEBA_SPLITS:
+        raise ValueError(f"CelebA split {split!r}: choose from {sorted(CELEBA_SPLITS)}")
+    names = []
+    with open(os.path.join(_celeba_dir(root), 'list_eval_partition.txt')) as f:
+        for line in f:
+            parts = line.split()
+            if len(parts) == 2 and parts[1] == CELEBA_SPLITS[split]:
+                names.append(parts[0])
+    return names
+
+
+def read_celeba_split(root, split, size=64, resize=None, workers=None, **unused):
+    """read_celeba for any split: (uint8 [N,size,size,3], int64 [N,40] attribute table) of partition `split`, with the same decode
+    pool, the same device resize_crop (unless the caller passes the host model as `resize`) and a cache file per split and size
+    beside the images (the train split's is read_celeba's own file)."""
+    names = celeba_split_files(root, split)
+    targets = celeba_attributes(root, names)
+    if targets.ndim != 2:
+        raise FileNotFoundError(f"{os.path.join(_celeba_dir(root), 'list_attr_celeba.txt')} not found: the split's targets are its attributes")
+    cache = os.path.join(_celeba_dir(root), f'img_align_celeba_{split}_{size}x{size}.npy')
+    if os.path.exists(cache):
+        images = np.load(cache)
+        if images.shape == (len(names), size, size, 3):
+            return images, targets
+    if resize is None:
+        from diagan.datasets.device import resize_crop
+
+        def resize(chunk):
+            return resize_crop(torch.from_numpy(chunk).cuda(), size).cpu().numpy()
+    images = np.concatenate([resize(chunk) for chunk in celeba_chunks(root, names, workers=workers)])
+    np.save(cache, images)
+    return images, targets
+
+
 READERS = {'cifar10': read_cifar10, 'color_mnist': read_color_mnist, 'mnist_fmnist': read_mnist_fmnist, 'celeba': read_celeba}
 
 
