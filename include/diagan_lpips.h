@@ -11,7 +11,8 @@
  * thread or one workgroup in an order fixed by the image's shape alone (no atomics, nothing depends on B): reruns are
  * bit-identical and an image's value does not depend on the batch it is in.
  * Every name of this part starts with diagan_lpips_ and returns int, except the workspace query.  The head of the attribute
- * classifier, which runs on the same VGG16 feature extractor, follows at the end of the file (diagan_attr_*).
+ * classifier, which runs on the same VGG16 feature extractor, follows (diagan_attr_*), and at the end of the file the PacGAN
+ * packing of the MNIST-DCGAN discriminator (diagan_pac_*), which shares nothing with VGG16 but this binding table.
  */
 #ifndef DIAGAN_LPIPS_H
 #define DIAGAN_LPIPS_H
@@ -118,6 +119,30 @@ int diagan_attr_ce(const float* logits, const int64_t* target, int M, int N, flo
 /* counter[0] += the number of rows of logits [M][N] whose first maximum is not at column 0 (a tie with column 0 counts as
  * class 0).  1 <= N <= 64.  One workgroup, as diagan_attr_ce. */
 int diagan_attr_count(const float* logits, int M, int N, int64_t* counter, void* stream);
+
+/* ---- PacGAN packing of the MNIST-DCGAN discriminator ----------------------------------------------------
+ *
+ * A discriminator built with num_pack = p judges p images at once: the batch of B images is cut into p chunks of n = B / p and
+ * chunk j is stacked on the channel axis behind chunk j - 1 (torch.cat(torch.split(x, n), dim=1) in NCHW).  The three entry
+ * points below are that rearrangement and its adjoint in this engine's layout, fp32 NHWC with padded channel counts:
+ * Cp = nc rounded up to a multiple of 4 for the images, Cq a multiple of 4 and >= nc p (the first convolution's padded input
+ * width) for the packed tensor.  They are declared in this header because the library's exports are the union of the headers
+ * and diagan/_native/lpips_abi.py is the table that takes additions; nothing here touches VGG16.  Same conventions as above.
+ * Pure data movement: every output value carries the bits of its source; one thread stores one 16-byte group of the output.
+ * Refused before any launch: a null pointer, p < 1, B not a multiple of p, Cp != r4(nc), Cq < nc p or not a multiple of 4, an
+ * output that is not 16-byte aligned.  Every name starts with diagan_pac_ and returns int.
+ */
+
+/* x [B][H][W][Cp] -> out [B / p][H][W][Cq]:  out[b][y][x][j nc + c] = x[j (B / p) + b][y][x][c]  for j < p, c < nc; the lanes
+ * nc p .. Cq - 1 are written as 0.0f (the first convolution multiplies them by its padded weight columns). */
+int diagan_pac_pack(const float* x, int B, int H, int W, int nc, int Cp, int p, int Cq, float* out, void* stream);
+
+/* The same from src [B][nc][H][W] (NCHW, unpadded): diagan_nchw_to_nhwc and diagan_pac_pack in one launch, for the real batch. */
+int diagan_pac_pack_nchw(const float* src, int B, int nc, int H, int W, int p, int Cq, float* out, void* stream);
+
+/* The adjoint: g [B / p][H][W][Cq] -> gx [B][H][W][Cp],  gx[j (B / p) + b][y][x][c] = g[b][y][x][j nc + c]  for c < nc; the lanes
+ * nc .. Cp - 1 are written as 0.0f (gx is the gradient of the generator's images: its tanh backward reads every lane). */
+int diagan_pac_unpack(const float* g, int B, int H, int W, int nc, int Cp, int p, int Cq, float* gx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 The reference's `train_mimicry_phase1.py` (flags :29-51, per-dataset schedule :82-92, trainer wiring :104-126) and
 `train_mimicry_phase2.py` (flags :39-56, scorer call :87-93, weighted sampler :21-34, trainer wiring :128-153) keep
 their flag names, defaults and on-disk layout; the scripts of the same names at the repository root are two-line
-wrappers around `phase1()` / `phase2()` below (further down: the colour-MNIST phases and the Inclusive GAN baseline).  Flags are declared as data (one table per phase plus the shared
+wrappers around `phase1()` / `phase2()` below (further down: the colour-MNIST phases, the Inclusive GAN baseline, the MNIST+FashionMNIST phases and the GOLD-only phase 2).  Flags are declared as data (one table per phase plus the shared
 ones) so that the contract is testable (`tests/test_host_logic.py` compares names and defaults).
 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N train_mimicry_phaseK.py ...` -- one process per GPU
@@ -312,7 +312,12 @@ def _single_process_pictures(args, run):
 
 
 def color_mnist_phase1(argv=None, dataset=None):
-    args = color_mnist_phase1_parser().parse_args(argv)
+    return _dcgan_phase1(color_mnist_phase1_parser().parse_args(argv), dataset, dict(save_eval_logits=False), True)
+
+
+def _dcgan_phase1(args, dataset, record_mode, closing_plot):
+    """Phase 1 of the mnist_dcgan pair.  `record_mode`: the trainer keywords that choose the mode of the logit record;
+    `closing_plot`: the colour-MNIST script's generator panels under --pictures."""
     run = _Run(args)
     _single_process_pictures(args, run)
     netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, num_pack=args.num_pack,
@@ -326,9 +331,9 @@ def color_mnist_phase1(argv=None, dataset=None):
     trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
                          optD=optD, optG=optG, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
                          vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
-                         device=run.device, topk=args.topk, save_logits=args.num_pack == 1, save_eval_logits=False)
+                         device=run.device, topk=args.topk, save_logits=args.num_pack == 1, **record_mode)
     trainer.train()
-    if args.pictures:                                   # train_mimicry_color_mnist_phase1.py:130
+    if args.pictures and closing_plot:                  # train_mimicry_color_mnist_phase1.py:130
         from diagan.utils.plot import plot_color_mnist_generator
         plot_color_mnist_generator(netG, save_path=run.save_path, file_name='eval_p1')
     return trainer
@@ -446,3 +451,181 @@ def inclusive(argv=None, dataset=None, inception=None, pictures=False):
         from diagan.utils.plot import plot_color_mnist_generator
         plot_color_mnist_generator(netG, save_path=run.save_path, file_name='eval_p1')
     return trainer
+
+
+# ---- MNIST+FashionMNIST front ends and the GOLD-only phase 2 -------------------------------------------------------------
+# train_mimicry_mnist_fmnist_phase1.py (flags :52-73, trainer wiring :115-132), train_mimicry_mnist_fmnist_phase2.py (flags :41-65,
+# scorer call :98-104, trainer wiring :133-158) and the two *_phase2_gold.py scripts (flags :38-58 / :38-61, trainer wiring
+# :110-131): the colour-MNIST scripts on the one-channel set, and a phase 2 that re-weights the discriminator loss (GOLD) in
+# place of resampling.  Each table is the reference script's parser plus the repository's --num_workers and --pictures, nothing
+# else (tests/test_pacgan_host.py compares them with tests/golden/cli_flags_mnist.json).
+# Parsed and never read, as in the reference: --quiet (the progress bar is the trainer's own business, DIAGAN_QUIET), --num_pack
+# and --use_clipping on every phase-2 script (their models are built unpacked and nothing clips), --resample_score,
+# --logit_save_steps and --use_eval_logits on the gold ones (they read no logit file and record none).
+_QUIET = (("--quiet",), False, _FLAG, "do not use pbar")
+_REPOSITORY_FLAGS = [
+    (("--num_workers",), 0, int, None),             # not in the reference
+    (("--pictures",), False, _FLAG, _PICTURES),
+]
+
+
+def _dcgan_table(dataset, root, exp_name, model, rows):
+    """The flags every mnist_dcgan script shares, in the defaults of one dataset, followed by the script's own rows."""
+    return [
+        (("--dataset", "-d"), dataset, str, None),
+        (("--root", "-r"), root, str, "dataset dir"),
+        (("--work_dir",), "./exp_results", str, "output dir"),
+        (("--exp_name",), exp_name, str, "exp name"),
+        (("--model",), model, str, "network model"),
+        (("--gpu",), "0", str, "id(s) for CUDA_VISIBLE_DEVICES (single process only)"),
+        (("--num_pack",), 1, int, None),
+        (("--batch_size",), 64, int, None),
+        (("--seed",), 1, int, None),
+        (("--use_clipping",), False, _FLAG, None),
+        (("--num_steps",), 20000, int, None),
+        (("--logit_save_steps",), 100, int, None),
+        (("--decay",), "None", str, None),
+        (("--n_dis",), 1, int, None),
+        (("--major_ratio",), 0.99, float, None),
+        (("--num_data",), 10000, int, None),
+    ] + rows + _REPOSITORY_FLAGS
+
+
+def _phase2_rows(baseline, loss_type):
+    return [
+        (("--baseline_exp_name",), baseline, str, "exp name"),
+        (("--p1_step",), 10000, int, None),
+        (("--loss_type",), loss_type, str, "loss type"),
+    ]
+
+
+_MF = ("mnist_fmnist", "./dataset/mnist_fmnist", "mnist_fmnist")
+MNIST_FMNIST_PHASE1 = _dcgan_table(*_MF, "mnist_dcgan", [
+    (("--loss_type",), "ns", str, "loss type"),
+    (("--topk",), 0, int, None),
+    (("--resample_score",), None, str, None),
+    _QUIET,
+])
+MNIST_FMNIST_PHASE2 = _dcgan_table(*_MF, "mnistgan", _phase2_rows("mnist_fmnist_baseline", "ns") + [
+    (("--resample_score",), None, str, None),
+    (("--use_eval_logits",), None, int, None),
+    (("--gold",), False, _FLAG, None),
+    _QUIET,
+])
+COLOR_MNIST_PHASE2_GOLD = _dcgan_table("color_mnist", "./dataset/colour_mnist", "colour_mnist", "mnistgan",
+                                       _phase2_rows("colour_mnist", "hinge") + [
+    (("--resample_score",), None, str, None),
+])
+MNIST_FMNIST_PHASE2_GOLD = _dcgan_table(*_MF, "mnistgan", _phase2_rows("mnist_fmnist_baseline", "ns") + [
+    (("--use_eval_logits",), None, int, None),
+    _QUIET,
+])
+
+
+def mnist_fmnist_phase1_parser():
+    return make_parser(MNIST_FMNIST_PHASE1)
+
+
+def mnist_fmnist_phase2_parser():
+    return make_parser(MNIST_FMNIST_PHASE2)
+
+
+def color_mnist_phase2_gold_parser():
+    return make_parser(COLOR_MNIST_PHASE2_GOLD)
+
+
+def mnist_fmnist_phase2_gold_parser():
+    return make_parser(MNIST_FMNIST_PHASE2_GOLD)
+
+
+def mnist_fmnist_phase1(argv=None, dataset=None):
+    """The colour-MNIST phase 1 on MNIST+FashionMNIST: the logit record in the trainer's default mode (eval; the reference's
+    script does not pass save_eval_logits, :115-132) and no closing generator plot."""
+    return _dcgan_phase1(mnist_fmnist_phase1_parser().parse_args(argv), dataset, {}, False)
+
+
+def mnist_fmnist_phase2(argv=None, dataset=None):
+    """Phase 2 on MNIST+FashionMNIST: resampling by --resample_score, D_drs, and with --gold the re-weighted discriminator
+    loss from --p1_step on.  Under --pictures the two opening plots only (the reference's closing ones are commented out)."""
+    args = mnist_fmnist_phase2_parser().parse_args(argv)
+    run = _Run(args)
+    _single_process_pictures(args, run)
+    baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
+    netG, netD, netD_drs, optG, optD, optD_drs = get_gan_model(dataset_name=args.dataset, model=args.model, drs=True,
+                                                               loss_type=args.loss_type)
+    start = {net: str(_checkpoint(baseline, net, args.p1_step)) for net in ('netG', 'netD')}
+    record = baseline / ('logits_netD_eval.pkl' if args.use_eval_logits == 1 else 'logits_netD_train.pkl')
+    print(f'Use logit from: {record}')
+    with open(record, "rb") as f:
+        logits = pickle.load(f)
+    if args.resample_score is None:       # the reference dies here with a KeyError on score_dict[None] (:104)
+        raise SystemExit("train_mimicry_mnist_fmnist_phase2.py needs --resample_score")
+    scores = calculate_scores(logits, start_epoch=args.p1_step - 5000, end_epoch=args.p1_step, device=run.device,
+                              keys=None if args.pictures else [args.resample_score])
+    weights = scores[args.resample_score]
+    print(f'sample_weights mean: {weights.mean()}, var: {weights.var()}, max: {weights.max()}, min: {weights.min()}')
+    print_num_params(netG, netD)
+
+    def fresh_set():
+        return get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
+                                      major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
+    loader = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers, weights=weights)
+    loader_drs = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers)
+    prefix = args.exp_name.split('/')[-1]
+    if args.pictures:                                   # train_mimicry_mnist_fmnist_phase2.py:124-127, draws included
+        from diagan.utils.plot import plot_data, plot_score_sort
+        imgs = next(iter(loader))[0]
+        plot_data(imgs, num_per_side=8, save_path=run.save_path, file_name=f'{prefix}_resampled_train_data_p2', vis=None)
+        plot_score_sort(loader.dataset, scores, save_path=run.save_path,
+                        phase=f'{prefix}_{args.p1_step - 5000}-{args.p1_step}_score', plot_metric_name=args.resample_score)
+    print(args, start['netG'], start['netD'], start['netD'])
+    trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
+                         optD=optD, optG=optG, netG_ckpt_file=start['netG'], netD_ckpt_file=start['netD'],
+                         netD_drs_ckpt_file=start['netD'], netD_drs=netD_drs, optD_drs=optD_drs,
+                         dataloader_drs=loader_drs, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
+                         vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
+                         device=run.device, save_logits=False, gold=args.gold, gold_step=args.p1_step)
+    trainer.train()
+    return trainer
+
+
+def _phase2_gold(args, dataset, data_plot, closing_plots):
+    """GOLD alone: the phase-1 pair goes on training on the uniform loader with the discriminator loss re-weighted from
+    --p1_step on.  No logit file, no scores, no D_drs.  `data_plot`: file name of the opening batch plot under --pictures."""
+    run = _Run(args)
+    _single_process_pictures(args, run)
+    baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
+    netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, loss_type=args.loss_type, gold=True)
+    start = {net: str(_checkpoint(baseline, net, args.p1_step)) for net in ('netG', 'netD')}
+    print_num_params(netG, netD)
+    train_set = get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
+                                       major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
+    loader = _plain_weighted_loader(train_set, args.batch_size, args.num_workers)
+    prefix = args.exp_name.split('/')[-1]
+    if args.pictures:                                   # *_phase2_gold.py:103-105 / :106-108, the draw included
+        from diagan.utils.plot import plot_data
+        imgs = next(iter(loader))[0]
+        plot_data(imgs, num_per_side=8, save_path=run.save_path, file_name=f'{prefix}_{data_plot}', vis=None)
+    print(args, start['netG'], start['netD'])
+    run.replicate(netG, netD)
+    trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
+                         optD=optD, optG=optG, netG_ckpt_file=start['netG'], netD_ckpt_file=start['netD'],
+                         n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000, vis_steps=100, lr_decay=args.decay,
+                         dataloader=loader, log_dir=run.out_dir, print_steps=10, device=run.device, save_logits=False,
+                         gold=True, gold_step=args.p1_step)
+    trainer.train()
+    if args.pictures and closing_plots:                 # train_mimicry_color_mnist_phase2_gold.py:134-138
+        from diagan.utils.plot import plot_color_mnist_generator
+        plot_color_mnist_generator(netG, save_path=run.save_path, file_name=f'{prefix}-eval_p2')
+        netG.restore_checkpoint(ckpt_file=start['netG'])
+        netG.to(run.device)
+        plot_color_mnist_generator(netG, save_path=run.save_path, file_name=f'{prefix}-eval_generated_p1')
+    return trainer
+
+
+def color_mnist_phase2_gold(argv=None, dataset=None):
+    return _phase2_gold(color_mnist_phase2_gold_parser().parse_args(argv), dataset, 'gold_train_data_p2', True)
+
+
+def mnist_fmnist_phase2_gold(argv=None, dataset=None):
+    return _phase2_gold(mnist_fmnist_phase2_gold_parser().parse_args(argv), dataset, 'resampled_train_data_p2', False)

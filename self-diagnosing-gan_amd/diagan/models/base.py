@@ -160,7 +160,7 @@ class BaseGenerator(BaseModel):
         output, dctx = netD.forward_nhwc(fake, netD.training, save=True, need_dgrad=True, need_in_dgrad=True)
         k = None
         if getattr(self, 'use_topk', False):          # get_topk, topk_models.py:31-38
-            k = int(self.topk_rate * batch_size)
+            k = int(self.topk_rate * output.shape[0])      # of the logits: a packed discriminator returns fewer than images
         errG, dlogit = E.loss_gen(output, self.loss_type, k=k)
         # backward: through D to the images (D's own weight gradients are dead values in the
         # reference -- zeroed at the next D step before use -- so they are not computed), then G
@@ -192,6 +192,11 @@ class BaseDiscriminator(BaseModel):
     #    and backward_nhwc(ctx, dlogit, need_wgrad, need_gx) -> g_x or None
     def to_nhwc(self, x):
         return E.nchw_to_nhwc(x.to(dtype=torch.float32), self.in_channels_padded)
+
+    def forward_real_nhwc(self, x, training, **kwargs):
+        """forward_nhwc on a real batch given as NCHW images.  A network whose forward_nhwc starts with a rearrangement of its own
+        (PacGAN packing, models/mnist.py) overrides it to convert the layout and rearrange in one launch."""
+        return self.forward_nhwc(self.to_nhwc(x), training, **kwargs)
 
     def forward(self, x):
         """images NCHW [n, C, H, W] -> logits [n, 1]."""
@@ -230,8 +235,8 @@ class BaseDiscriminator(BaseModel):
                                     d_fake=dl[B:])
             self.backward_nhwc(ctx, dl, need_wgrad=True, need_gx=False)
         else:
-            out_real, ctx_r = self.forward_nhwc(self.to_nhwc(real_images), self.training, save=True, need_dgrad=True,
-                                                need_in_dgrad=False)
+            out_real, ctx_r = self.forward_real_nhwc(real_images, self.training, save=True, need_dgrad=True,
+                                                     need_in_dgrad=False)
             fake, _ = netG.generate_images_nhwc(batch_size, device=device, noise=noise, save=False)   # .detach()
             out_fake, ctx_f = self.forward_nhwc(fake, self.training, save=True, need_dgrad=True, need_in_dgrad=False,
                                                 slot=1)

@@ -21,6 +21,7 @@ from diagan.models.layers import BatchNorm, ConvLayer, LatentLinear, _r4
 from diagan.models.topk_models import TopKGenerator
 from diagan.ops import conv as C
 from diagan.ops import eltwise as E
+from diagan.ops import pacgan as P
 
 
 def _bn_pro(bn):
@@ -139,16 +140,24 @@ class MNIST_DCGAN_Discriminator(BaseDiscriminator):
         self.use_gold = use_gold
         self._link_layers()
 
-    # ---- PacGAN packing (mnist.py:213-216): chunks of the batch concatenated on the channel axis
+    # ---- PacGAN packing (mnist.py:213-216): chunks of the batch concatenated on the channel axis, one launch (ops/pacgan.py)
     def _pack_nhwc(self, x):
         if self.num_pack == 1:
             return x
-        parts = torch.split(x[..., : self.nc], int(x.size(0) / self.num_pack))
-        x = torch.cat(parts, dim=-1)
-        return torch.nn.functional.pad(x, (0, _r4(self.nc * self.num_pack) - x.shape[-1])).contiguous()
+        return P.pac_pack(x, self.nc, self.num_pack)
 
-    def forward_nhwc(self, x, training, save=True, need_dgrad=True, need_in_dgrad=True, slot=0, drop_masks=None):
-        x = self._pack_nhwc(x)
+    def forward_real_nhwc(self, x, training, **kwargs):
+        """A packed discriminator takes its real batch from NCHW to the packed NHWC tensor in one launch."""
+        if self.num_pack == 1:
+            return BaseDiscriminator.forward_real_nhwc(self, x, training, **kwargs)
+        return self._forward_packed(P.pac_pack_nchw(x.to(dtype=torch.float32), self.num_pack), training, **kwargs)
+
+    def forward_nhwc(self, x, training, **kwargs):
+        """x: B images [B, H, W, r4(nc)].  The logits, the dropout masks and the BatchNorm statistics are those of the
+        B / num_pack packed images."""
+        return self._forward_packed(self._pack_nhwc(x), training, **kwargs)
+
+    def _forward_packed(self, x, training, save=True, need_dgrad=True, need_in_dgrad=True, slot=0, drop_masks=None):
         h, saved = x, []
         # the keep-masks of ALL layers of this forward from ONE bernoulli_ launch over a flat buffer (round 5: eight launches
         # before), cut in the layers' activation sizes
@@ -190,7 +199,7 @@ class MNIST_DCGAN_Discriminator(BaseDiscriminator):
         xn = self.to_nhwc(x)
         if get_feature:       # NCHW-flattened 8192-vector of the last activation (mnist.py:218-221)
             _, ctx = self.forward_nhwc(xn, self.training, save=True, need_dgrad=False)
-            B = xn.shape[0]
+            B = ctx['flat'].shape[0]          # the packed batch: B / num_pack rows, as the reference returns
             return ctx['flat'].view(B, 16, 512).permute(0, 2, 1).reshape(B, -1).contiguous()
         logit, _ = self.forward_nhwc(xn, self.training, save=False, need_dgrad=False)
         return logit
@@ -217,6 +226,6 @@ class MNIST_DCGAN_Discriminator(BaseDiscriminator):
                 g = None
         if need_wgrad:
             self.wgrad_batch.finish(0)
-        if g is not None and self.num_pack > 1:
-            raise NotImplementedError("image gradient through PacGAN packing (num_pack > 1) is not implemented")
+        if g is not None and self.num_pack > 1:      # back to one gradient per image, the pad lanes zero (tanh_bwd reads them)
+            g = P.pac_unpack(g, self.nc, self.num_pack)
         return g
