@@ -12,7 +12,8 @@
  * bit-identical and an image's value does not depend on the batch it is in.
  * Every name of this part starts with diagan_lpips_ and returns int, except the workspace query.  The head of the attribute
  * classifier, which runs on the same VGG16 feature extractor, follows (diagan_attr_*), and at the end of the file the PacGAN
- * packing of the MNIST-DCGAN discriminator (diagan_pac_*), which shares nothing with VGG16 but this binding table.
+ * packing of the MNIST-DCGAN discriminator (diagan_pac_*), which shares nothing with VGG16 but this binding table, and the head
+ * of the SimpleConvNet group classifier (diagan_cls_*), which shares the loss with the attribute classifier.
  */
 #ifndef DIAGAN_LPIPS_H
 #define DIAGAN_LPIPS_H
@@ -143,6 +144,42 @@ int diagan_pac_pack_nchw(const float* src, int B, int nc, int H, int W, int p, i
 /* The adjoint: g [B / p][H][W][Cq] -> gx [B][H][W][Cp],  gx[j (B / p) + b][y][x][c] = g[b][y][x][j nc + c]  for c < nc; the lanes
  * nc .. Cp - 1 are written as 0.0f (gx is the gradient of the generator's images: its tanh backward reads every lane). */
 int diagan_pac_unpack(const float* g, int B, int H, int W, int nc, int Cp, int p, int Cq, float* gx, void* stream);
+
+/* ---- the head of the SimpleConvNet group classifier -----------------------------------------------------
+ *
+ * The classifier's four 7 x 7 convolutions, their BatchNorm and the loss run on entry points that exist (diagan_conv_gemm,
+ * diagan_bn_*, diagan_conv_wgrad, diagan_attr_ce); the three below add the end of the network: the last BatchNorm + ReLU, the
+ * global mean, Linear(C, N) and F.normalize in one read of the last convolution's output, the adjoint of the mean and the linear
+ * layer, and the histogram of the predicted labels.  Conventions of the diagan_attr_* section: fp32, row-major, contiguous, no
+ * atomics, no allocation; every output element is formed in an order fixed by the shapes alone, and in the forward pass a row's
+ * values do not depend on the other rows of the batch.  Every name starts with diagan_cls_ and returns int.
+ */
+
+/* x [B][HW][C], the last convolution's raw output; scale, shift [C] the BatchNorm of it as an affine map; w [N][C], bias [N].
+ *   pooled[b][c] = (1 / HW) sum_p max(scale[c] x[b][p][c] + shift[c], 0)        (one fma per term; fp32 sums)
+ *   logits[b][n] = sum_c pooled[b][c] w[n][c] + bias[n]                         (fp32)
+ *   feat[b][c]   = pooled[b][c] / max(|pooled[b]|_2, 1e-12)                      (F.normalize(dim=1))
+ * The norm is computed in FLOAT64: the squares, their sum and the square root; the division is a float64 division rounded to fp32
+ * once.  An all-zero pooled row gives feat = 0.
+ * A workgroup per image: 256 / (C / 4) rows of lanes each walk a fixed stride of the pixels with 16-byte loads, and the rows'
+ * sums are added in row order.  C a multiple of 4, 4 <= C <= 1024; 1 <= N <= 64; HW >= 1; x, scale, shift 16-byte aligned.
+ * logits may be NULL (then w and bias are not read), feat may be NULL; pooled is always written. */
+int diagan_cls_head_fwd(const float* x, const float* scale, const float* shift, const float* w, const float* bias, int B, int HW,
+                        int C, int N, float* pooled, float* logits, float* feat, void* stream);
+
+/* The adjoint, from dlogit [B][N]:
+ *   g[b][p][c] = (1 / HW) sum_n dlogit[b][n] w[n][c]   for every p, the sum with n ascending; the same bits at every p
+ *   gw[n][c]   = sum_b dlogit[b][n] pooled[b][c],   gb[n] = sum_b dlogit[b][n],   b ascending
+ * g is the gradient with respect to the ReLU's OUTPUT: the ReLU gate and the BatchNorm backward are diagan_bn_bwd(relu = 1) on g
+ * and the saved x.  g may be NULL (weights only; then w is not read); gw and gb may each be NULL (then pooled is not read
+ * without gw).  gw and gb are overwritten, not accumulated.  Same shape limits; B <= 65535; g 16-byte aligned. */
+int diagan_cls_head_bwd(const float* dlogit, const float* w, const float* pooled, int B, int HW, int C, int N, float* g, float* gw,
+                        float* gb, void* stream);
+
+/* counts[n] += the number of rows of logits [M][N] whose FIRST maximum is at column n (torch.max(dim=1)'s rule, as diagan_attr_ce
+ * states it: only a greater value replaces the maximum).  counts int64 [N], 8-byte aligned; 1 <= N <= 64.  One workgroup; lane n
+ * alone reads and writes counts[n], so successive launches on a stream add up. */
+int diagan_cls_histogram(const float* logits, int M, int N, int64_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -163,13 +163,13 @@ def train_convnet_celeba(argv=None):
     train(train_parser().parse_args(argv))
 
 
-def count(args, hidden=4096, classifier_path=SAVE_PATH, dataset_name='celeba'):
-    """The body of count_attr_celeba -> (attr_num, not_attr_num)."""
-    from diagan.models.attr_classifier import VGG16AttrClassifier
+def load_generator(args, dataset_name):
+    """The generator side of the counting command lines (count_attr_celeba here, count_group in feature_cli.py): seeds, builds
+    the networks of `dataset_name`, restores the checkpoints of --netG_ckpt_step and wraps the generator in DRS with --drs.
+    -> (netG, save_path, step, device)."""
     from diagan.models.drs import DRS
     from diagan.models.predefined_models import get_gan_model
     from diagan.utils.settings import set_seed
-    _check_model(args.classifier, '--classifier')
     if args.gpu:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     if not args.netG_ckpt_step:
@@ -199,6 +199,14 @@ def count(args, hidden=4096, classifier_path=SAVE_PATH, dataset_name='celeba'):
     if args.drs:
         netD_drs.restore_checkpoint(ckpt_file=f'{save_path}/checkpoints/{net_d}/{net_d}_{step}_steps.pth')
         netG = DRS(netG=netG, netD=netD_drs, device=device)
+    return netG, save_path, step, device
+
+
+def count(args, hidden=4096, classifier_path=SAVE_PATH, dataset_name='celeba'):
+    """The body of count_attr_celeba -> (attr_num, not_attr_num)."""
+    from diagan.models.attr_classifier import VGG16AttrClassifier
+    _check_model(args.classifier, '--classifier')
+    netG, save_path, step, device = load_generator(args, dataset_name)
 
     print('Load classifier')
     model = VGG16AttrClassifier(weights='random', hidden=hidden)

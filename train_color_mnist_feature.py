@@ -1,0 +1,11 @@
+#!/usr/bin/env python
+"""Trains the SimpleConvNet group classifier on Colored MNIST (the reference's script of this name): see diagan/feature_cli.py."""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "self-diagnosing-gan_amd"))
+
+from diagan.feature_cli import train_color_mnist_feature as main  # noqa: E402
+
+if __name__ == '__main__':
+    main()
