@@ -9,13 +9,13 @@ count_attr_celeba      classifies --num_samples generated images, with or withou
 
 Both keep the loss, the correct-count and the attribute count in device accumulators that are read once per epoch or per run; the
 reference calls .item() every batch."""
-import csv
 import os
 import time
 
 import torch
 
 from diagan.cli import _FLAG, make_parser
+from diagan.front_end import append_count_row, append_row, count_generated, load_generator
 
 # train_convnet_celeba.py:66-72
 TRAIN_FLAGS = [
@@ -67,16 +67,6 @@ def _check_model(name, flag):
                                   f"(torchvision's {name} has no `classifier`), so only vgg16 ever ran")
     if name != 'vgg16':
         raise ValueError('model should be vgg16 or resnet18 or inception')
-
-
-def append_row(csv_file, header, row):
-    """The reference's CSV habit: a new file gets the header first, an existing one only the row."""
-    fresh = not os.path.exists(csv_file)
-    with open(csv_file, 'w' if fresh else 'a', newline='') as f:
-        wr = csv.writer(f)
-        if fresh:
-            wr.writerow(header)
-        wr.writerow(row)
 
 
 def train_csv_row(attr, train, valid, test):
@@ -163,45 +153,6 @@ def train_convnet_celeba(argv=None):
     train(train_parser().parse_args(argv))
 
 
-def load_generator(args, dataset_name):
-    """The generator side of the counting command lines (count_attr_celeba here, count_group in feature_cli.py): seeds, builds
-    the networks of `dataset_name`, restores the checkpoints of --netG_ckpt_step and wraps the generator in DRS with --drs.
-    -> (netG, save_path, step, device)."""
-    from diagan.models.drs import DRS
-    from diagan.models.predefined_models import get_gan_model
-    from diagan.utils.settings import set_seed
-    if args.gpu:
-        os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    if not args.netG_ckpt_step:
-        raise SystemExit("--netG_ckpt_step is required")
-    if not torch.cuda.is_available():
-        raise SystemExit("counting runs on the HIP engine and needs a GPU")
-    set_seed(args.seed)
-    print(args)
-    save_path = f'{args.work_dir}/{args.exp_name}'
-    device = 'cuda'
-
-    print(f'load model from {save_path} step: {args.netG_ckpt_step}')
-    nets = get_gan_model(dataset_name=dataset_name, model=args.model, loss_type=args.loss_type, drs=args.drs)
-    netG, netD_drs = nets[0], (nets[2] if args.drs else None)
-    netG.to(device)
-    if not args.netG_train_mode:
-        netG.eval()
-        if netD_drs is not None:
-            netD_drs.eval()
-    if netD_drs is not None:
-        netD_drs.to(device)
-    step = args.netG_ckpt_step
-    gan_ckpt = f'{save_path}/checkpoints/netG/netG_{step}_steps.pth'
-    net_d = 'netD' if args.use_original_netD else 'netD_drs'
-    print(gan_ckpt)
-    netG.restore_checkpoint(ckpt_file=gan_ckpt)
-    if args.drs:
-        netD_drs.restore_checkpoint(ckpt_file=f'{save_path}/checkpoints/{net_d}/{net_d}_{step}_steps.pth')
-        netG = DRS(netG=netG, netD=netD_drs, device=device)
-    return netG, save_path, step, device
-
-
 def count(args, hidden=4096, classifier_path=SAVE_PATH, dataset_name='celeba'):
     """The body of count_attr_celeba -> (attr_num, not_attr_num)."""
     from diagan.models.attr_classifier import VGG16AttrClassifier
@@ -213,20 +164,11 @@ def count(args, hidden=4096, classifier_path=SAVE_PATH, dataset_name='celeba'):
     model.load_state_dict(torch.load(os.path.join(classifier_path, f'{args.attr}.pth'), map_location='cpu', weights_only=True))
     model.to(device).eval()
 
-    batch_size = min(args.batch_size, args.num_samples)
-    num_batches = args.num_samples // batch_size
-    model.counter().zero_()
-    for _ in range(num_batches):
-        with torch.no_grad():
-            model.count(netG.generate_images(batch_size, device=device).float().contiguous())      # straight into the classifier
-    attr_num = int(model.counter().item())                                                         # the one read
-    not_attr_num = num_batches * batch_size - attr_num
+    (attr_num,), total = count_generated(args, netG, model, model.counter(), device)
+    not_attr_num = total - attr_num
     print(f'attr: {attr_num}')
     print(f'not attr: {not_attr_num}')
-
-    output_dir = os.path.join(save_path, 'evaluate', f'step-{step}')
-    os.makedirs(output_dir, exist_ok=True)
-    append_row(os.path.join(output_dir, 'count_attribute.csv'), COUNT_CSV_HEADER, [args.attr, attr_num, not_attr_num])
+    append_count_row(save_path, step, 'count_attribute.csv', COUNT_CSV_HEADER, [args.attr, attr_num, not_attr_num])
     return attr_num, not_attr_num
 
 

@@ -10,21 +10,16 @@ Multi-GPU: `python -m torch.distributed.run --nproc-per-node N train_mimicry_pha
 over RCCL; `--batch_size` is per GPU; `--gpu` only applies to a single process.
 """
 import argparse
-import os
-import pickle
 from pathlib import Path
 
-import torch
 from torch.utils import data
 
-from diagan.datasets.device import DeviceImages, DeviceLoader
 from diagan.datasets.predefined import get_predefined_dataset
-from diagan.datasets.sampler import ShardedSampler, make_weighted_sampler
+from diagan.datasets.sampler import make_weighted_sampler
+from diagan.front_end import Run, read_logit_record, score_logit_record, sharded_loader
 from diagan.models.predefined_models import get_gan_model
-from diagan.trainer import distributed as dist
 from diagan.trainer.trainer import LogTrainer
-from diagan.utils.plot import calculate_scores, print_num_params
-from diagan.utils.settings import set_seed
+from diagan.utils.plot import print_num_params
 
 _FLAG = "store_true"     # marker for boolean switches in the tables below
 # not in the reference, which always draws them: they take draws from the global generators (a batch of the loader,
@@ -104,62 +99,30 @@ def phase2_parser():
 
 def make_loader(dataset, batch_size, num_workers=0, weights=None, floor=1e-6):
     """Phase 1: uniform shuffling.  Phase 2: `WeightedRandomSampler` over weights floored at 1e-6
-    (train_mimicry_phase2.py:21-34).  Under data parallelism every rank walks the SAME sampler order (shared CPU
-    seed) and keeps every W-th index, so the phase-2 weights stay in force on every rank (the reference's DDP path
-    drops them)."""
-    sampler = None if weights is None else make_weighted_sampler(weights, floor)
-    world = dist.get_world_size()
-    if world > 1:
-        sampler = ShardedSampler(sampler if sampler is not None else data.RandomSampler(dataset), dist.get_rank(), world)
-    # pinned staging only with worker processes (the reference always runs 8 of them): in the main process every
-    # batch would pay a synchronous host allocation (~2 ms per tensor, 40 ms per global step)
-    return _loader(dataset, batch_size, sampler, num_workers)
+    (train_mimicry_phase2.py:21-34).  Sharded over the ranks by front_end.sharded_loader."""
+    return sharded_loader(dataset, batch_size, num_workers, None if weights is None else make_weighted_sampler(weights, floor))
 
 
-def _loader(dataset, batch_size, sampler, num_workers):
-    """A device-resident dataset (datasets/device.py) is served by its own loader: same index stream, batches by one fetch launch."""
-    if isinstance(getattr(dataset, 'dataset', None), DeviceImages):
-        return DeviceLoader(dataset, batch_size, sampler=sampler)
-    return data.DataLoader(dataset=dataset, batch_size=batch_size, shuffle=sampler is None, sampler=sampler,
-                           num_workers=num_workers, pin_memory=num_workers > 0)
-
-
-class _Run:
-    """Process / device / output-directory state shared by both phases."""
-
-    def __init__(self, args):
-        self.rank, self.local_rank, self.world = dist.init_from_env()
-        if self.world == 1:
-            os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-        self.out_dir = f'{args.work_dir}/{args.exp_name}'
-        self.save_path = Path(self.out_dir)
-        self.save_path.mkdir(parents=True, exist_ok=True)
-        set_seed(args.seed)
-        self.seed = args.seed
-        if not torch.cuda.is_available():
-            raise SystemExit("the Dia-GAN engine needs an MI355X (no CPU fallback)")
-        index = self.local_rank % torch.cuda.device_count() if self.world > 1 else 0
-        self.device = torch.device("cuda", index)
-        torch.cuda.set_device(self.device)
-
-    def replicate(self, *nets):
-        """Data parallel start: identical parameters and buffers on every rank."""
-        if self.world > 1:
-            for net in nets:
-                net.to(self.device)
-                dist.broadcast_module_(net)
-            # identical replicas, different latent noise / dropout masks per rank (the CPU generators stay shared)
-            dist.seed_device_per_rank(self.seed)
+def _run(args):
+    """A trainer's run (front_end.Run): one process per GPU, output under <work_dir>/<exp_name>."""
+    return Run(args, no_gpu="the Dia-GAN engine needs an MI355X (no CPU fallback)", out_dir=f'{args.work_dir}/{args.exp_name}',
+               distributed=True)
 
 
 def _checkpoint(root, net, step):
     return root / f'checkpoints/{net}/{net}_{step}_steps.pth'
 
 
+def _phase1_files(args):
+    """-> (directory of the phase-1 run, its netG / netD checkpoint files of --p1_step): where every phase 2 starts"""
+    baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
+    return baseline, {net: str(_checkpoint(baseline, net, args.p1_step)) for net in ('netG', 'netD')}
+
+
 def phase1(argv=None):
     """Train G/D and record per-sample discriminator logits."""
     args = phase1_parser().parse_args(argv)
-    run = _Run(args)
+    run = _run(args)
     netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, loss_type=args.loss_type,
                                            topk=args.topk)
     print_num_params(netG, netD)
@@ -194,25 +157,17 @@ def phase1(argv=None):
 def phase2(argv=None):
     """Score the phase-1 logit record, resample by the score, fine-tune G/D and train the DRS discriminator."""
     args = phase2_parser().parse_args(argv)
-    run = _Run(args)
-    baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
+    run = _run(args)
+    baseline, start = _phase1_files(args)
 
     weights = None
-    if not args.gold:
-        record = baseline / 'logits_netD_eval.pkl'
-        print(f'Use logit from: {record}')
-        with open(record, "rb") as f:
-            logits = pickle.load(f)
-        # window [p1_step - 5000, p1_step) of the record (train_mimicry_phase2.py:90-92); scored on the device
-        scores = calculate_scores(logits, start_epoch=args.p1_step - args.window, end_epoch=args.p1_step,
-                                  device=run.device, keys=[args.resample_score])
-        weights = scores[args.resample_score]
-        print(f'sample_weights mean: {weights.mean()}, var: {weights.var()}, max: {weights.max()}, min: {weights.min()}')
+    if not args.gold:       # window [p1_step - 5000, p1_step) of the record (train_mimicry_phase2.py:90-92)
+        weights = score_logit_record(baseline / 'logits_netD_eval.pkl', args.p1_step, args.window, run.device,
+                                     keys=[args.resample_score], show=args.resample_score)[args.resample_score]
 
     netG, netD, netD_drs, optG, optD, optD_drs = get_gan_model(dataset_name=args.dataset, model=args.model,
                                                                loss_type=args.loss_type, drs=True, topk=args.topk,
                                                                gold=args.gold)
-    start = {net: str(_checkpoint(baseline, net, args.p1_step)) for net in ('netG', 'netD')}
     drs_start = start['netD']               # sic: D_drs starts from the phase-1 netD file (reference :100-101)
     print(f'model: {args.model} - netD_drs_ckpt_path: {drs_start}')
     print_num_params(netG, netD)
@@ -298,11 +253,13 @@ def floor_or_clip_weights(weights, clip=False, eps=1e-1):
 
 def _plain_weighted_loader(dataset, batch_size, num_workers, weights=None):
     """the colour-MNIST scripts hand the weights to WeightedRandomSampler as they are (phase 2 :24-37)"""
-    sampler = None if weights is None else data.WeightedRandomSampler(weights, len(weights), replacement=True)
-    world = dist.get_world_size()
-    if world > 1:
-        sampler = ShardedSampler(sampler if sampler is not None else data.RandomSampler(dataset), dist.get_rank(), world)
-    return _loader(dataset, batch_size, sampler, num_workers)
+    return sharded_loader(dataset, batch_size, num_workers,
+                          None if weights is None else data.WeightedRandomSampler(weights, len(weights), replacement=True))
+
+
+def _dcgan_set(args, dataset):
+    return get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None, major_ratio=args.major_ratio,
+                                  num_data=args.num_data, dataset=dataset)
 
 
 def _single_process_pictures(args, run):
@@ -318,22 +275,25 @@ def color_mnist_phase1(argv=None, dataset=None):
 def _dcgan_phase1(args, dataset, record_mode, closing_plot):
     """Phase 1 of the mnist_dcgan pair.  `record_mode`: the trainer keywords that choose the mode of the logit record;
     `closing_plot`: the colour-MNIST script's generator panels under --pictures."""
-    run = _Run(args)
+    run = _run(args)
     _single_process_pictures(args, run)
     netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, num_pack=args.num_pack,
                                            loss_type=args.loss_type, topk=args.topk == 1)
     print_num_params(netG, netD)
-    train_set = get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
-                                       major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
-    loader = _plain_weighted_loader(train_set, args.batch_size, args.num_workers)
+    loader = _plain_weighted_loader(_dcgan_set(args, dataset), args.batch_size, args.num_workers)
     print(args)
     run.replicate(netG, netD)
+    return _dcgan_phase1_train(args, run, netG, netD, optG, optD, loader, record_mode, args.pictures and closing_plot)
+
+
+def _dcgan_phase1_train(args, run, netG, netD, optG, optD, loader, record_mode, closing_plot):
+    """The trainer of _dcgan_phase1 and of inclusive(), and the closing generator panels (train_mimicry_color_mnist_phase1.py:130)."""
     trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
                          optD=optD, optG=optG, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
                          vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
                          device=run.device, topk=args.topk, save_logits=args.num_pack == 1, **record_mode)
     trainer.train()
-    if args.pictures and closing_plot:                  # train_mimicry_color_mnist_phase1.py:130
+    if closing_plot:
         from diagan.utils.plot import plot_color_mnist_generator
         plot_color_mnist_generator(netG, save_path=run.save_path, file_name='eval_p1')
     return trainer
@@ -341,28 +301,28 @@ def _dcgan_phase1(args, dataset, record_mode, closing_plot):
 
 def color_mnist_phase2(argv=None, dataset=None):
     args = color_mnist_phase2_parser().parse_args(argv)
-    run = _Run(args)
+    return _dcgan_phase2(args, dataset, None, True, compat_fetch_quirk=args.compat_fetch_quirk)
+
+
+def _dcgan_phase2(args, dataset, needs_score, closing_plots, **trainer_keywords):
+    """Phase 2 of the mnist_dcgan pair: resampling by --resample_score and D_drs.  `needs_score`: None, or the exit message for a
+    command line without --resample_score; `closing_plots`: the colour-MNIST script's generator panels under --pictures;
+    `trainer_keywords`: what the script hands to its trainer beyond the common keywords."""
+    run = _run(args)
     _single_process_pictures(args, run)
-    baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
+    baseline, start = _phase1_files(args)
     netG, netD, netD_drs, optG, optD, optD_drs = get_gan_model(dataset_name=args.dataset, model=args.model, drs=True,
                                                                loss_type=args.loss_type)
-    start = {net: str(_checkpoint(baseline, net, args.p1_step)) for net in ('netG', 'netD')}
     record = baseline / ('logits_netD_eval.pkl' if args.use_eval_logits == 1 else 'logits_netD_train.pkl')
-    print(f'Use logit from: {record}')
-    with open(record, "rb") as f:
-        logits = pickle.load(f)
-    scores = calculate_scores(logits, start_epoch=args.p1_step - 5000, end_epoch=args.p1_step, device=run.device,
-                              keys=None if args.resample_score is None or args.pictures else [args.resample_score])
+    if args.resample_score is None and needs_score:     # the exit comes once the record has been read
+        read_logit_record(record)
+        raise SystemExit(needs_score)
+    scores = score_logit_record(record, args.p1_step, 5000, run.device, show=args.resample_score,
+                                keys=None if args.resample_score is None or args.pictures else [args.resample_score])
     weights = scores[args.resample_score] if args.resample_score is not None else None
-    if weights is not None:
-        print(f'sample_weights mean: {weights.mean()}, var: {weights.var()}, max: {weights.max()}, min: {weights.min()}')
     print_num_params(netG, netD)
-
-    def fresh_set():
-        return get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
-                                      major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
-    loader = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers, weights=weights)
-    loader_drs = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers)
+    loader = _plain_weighted_loader(_dcgan_set(args, dataset), args.batch_size, args.num_workers, weights=weights)
+    loader_drs = _plain_weighted_loader(_dcgan_set(args, dataset), args.batch_size, args.num_workers)
     prefix = args.exp_name.split('/')[-1]
     if args.pictures and args.resample_score is not None:      # train_mimicry_color_mnist_phase2.py:119-122, draws included
         from diagan.utils.plot import plot_data, plot_score_sort
@@ -376,9 +336,9 @@ def color_mnist_phase2(argv=None, dataset=None):
                          netD_drs_ckpt_file=start['netD'], netD_drs=netD_drs, optD_drs=optD_drs,
                          dataloader_drs=loader_drs, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
                          vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
-                         device=run.device, save_logits=False, compat_fetch_quirk=args.compat_fetch_quirk)
+                         device=run.device, save_logits=False, **trainer_keywords)
     trainer.train()
-    if args.pictures:                                   # train_mimicry_color_mnist_phase2.py:154-164
+    if args.pictures and closing_plots:                 # train_mimicry_color_mnist_phase2.py:154-164
         from diagan.models.drs import DRS
         from diagan.utils.plot import plot_color_mnist_generator
         plot_color_mnist_generator(netG, save_path=run.save_path, file_name=f'{prefix}-eval_p2')
@@ -429,12 +389,12 @@ def inclusive(argv=None, dataset=None, inception=None, pictures=False):
     """`inception`: a ready InceptionV3 or weights object in place of --inception_weights (tests).  `pictures`: draw the
     reference's closing sample panels (eval_p1_all / _green / _red .jpg), which take draws from the global generators."""
     args = inclusive_parser().parse_args(argv)
-    run = _Run(args)
+    run = _run(args)
     if run.world > 1:
         raise NotImplementedError("train_mimicry_inclusive.py is single-GPU, as in the reference")
-    train_set = get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
-                                       major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
-    loader = _plain_weighted_loader(train_set, args.batch_size, args.num_workers)
+    # the generator takes the loader, so the loader comes first here; _dcgan_phase1 builds its networks first, and that order is the
+    # order of the random draws: the two keep their own opening lines
+    loader = _plain_weighted_loader(_dcgan_set(args, dataset), args.batch_size, args.num_workers)
     netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, num_pack=args.num_pack,
                                            loss_type=args.loss_type, topk=args.topk == 1, inclusive=True,
                                            num_data=args.num_data, dataloader=loader,
@@ -442,15 +402,7 @@ def inclusive(argv=None, dataset=None, inception=None, pictures=False):
                                            latent_factor=args.latent_factor)
     print_num_params(netG, netD)
     print(args)
-    trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
-                         optD=optD, optG=optG, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
-                         vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
-                         device=run.device, topk=args.topk, save_logits=args.num_pack == 1, save_eval_logits=False)
-    trainer.train()
-    if pictures:                                        # train_mimicry_inclusive.py:134
-        from diagan.utils.plot import plot_color_mnist_generator
-        plot_color_mnist_generator(netG, save_path=run.save_path, file_name='eval_p1')
-    return trainer
+    return _dcgan_phase1_train(args, run, netG, netD, optG, optD, loader, dict(save_eval_logits=False), pictures)  # :113-134
 
 
 # ---- MNIST+FashionMNIST front ends and the GOLD-only phase 2 -------------------------------------------------------------
@@ -548,59 +500,20 @@ def mnist_fmnist_phase2(argv=None, dataset=None):
     """Phase 2 on MNIST+FashionMNIST: resampling by --resample_score, D_drs, and with --gold the re-weighted discriminator
     loss from --p1_step on.  Under --pictures the two opening plots only (the reference's closing ones are commented out)."""
     args = mnist_fmnist_phase2_parser().parse_args(argv)
-    run = _Run(args)
-    _single_process_pictures(args, run)
-    baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
-    netG, netD, netD_drs, optG, optD, optD_drs = get_gan_model(dataset_name=args.dataset, model=args.model, drs=True,
-                                                               loss_type=args.loss_type)
-    start = {net: str(_checkpoint(baseline, net, args.p1_step)) for net in ('netG', 'netD')}
-    record = baseline / ('logits_netD_eval.pkl' if args.use_eval_logits == 1 else 'logits_netD_train.pkl')
-    print(f'Use logit from: {record}')
-    with open(record, "rb") as f:
-        logits = pickle.load(f)
-    if args.resample_score is None:       # the reference dies here with a KeyError on score_dict[None] (:104)
-        raise SystemExit("train_mimicry_mnist_fmnist_phase2.py needs --resample_score")
-    scores = calculate_scores(logits, start_epoch=args.p1_step - 5000, end_epoch=args.p1_step, device=run.device,
-                              keys=None if args.pictures else [args.resample_score])
-    weights = scores[args.resample_score]
-    print(f'sample_weights mean: {weights.mean()}, var: {weights.var()}, max: {weights.max()}, min: {weights.min()}')
-    print_num_params(netG, netD)
-
-    def fresh_set():
-        return get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
-                                      major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
-    loader = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers, weights=weights)
-    loader_drs = _plain_weighted_loader(fresh_set(), args.batch_size, args.num_workers)
-    prefix = args.exp_name.split('/')[-1]
-    if args.pictures:                                   # train_mimicry_mnist_fmnist_phase2.py:124-127, draws included
-        from diagan.utils.plot import plot_data, plot_score_sort
-        imgs = next(iter(loader))[0]
-        plot_data(imgs, num_per_side=8, save_path=run.save_path, file_name=f'{prefix}_resampled_train_data_p2', vis=None)
-        plot_score_sort(loader.dataset, scores, save_path=run.save_path,
-                        phase=f'{prefix}_{args.p1_step - 5000}-{args.p1_step}_score', plot_metric_name=args.resample_score)
-    print(args, start['netG'], start['netD'], start['netD'])
-    trainer = LogTrainer(output_path=run.save_path, logit_save_steps=args.logit_save_steps, netD=netD, netG=netG,
-                         optD=optD, optG=optG, netG_ckpt_file=start['netG'], netD_ckpt_file=start['netD'],
-                         netD_drs_ckpt_file=start['netD'], netD_drs=netD_drs, optD_drs=optD_drs,
-                         dataloader_drs=loader_drs, n_dis=args.n_dis, num_steps=args.num_steps, save_steps=1000,
-                         vis_steps=100, lr_decay=args.decay, dataloader=loader, log_dir=run.out_dir, print_steps=10,
-                         device=run.device, save_logits=False, gold=args.gold, gold_step=args.p1_step)
-    trainer.train()
-    return trainer
+    # without --resample_score the reference dies with a KeyError on score_dict[None] (:104)
+    return _dcgan_phase2(args, dataset, "train_mimicry_mnist_fmnist_phase2.py needs --resample_score", False, gold=args.gold,
+                         gold_step=args.p1_step)
 
 
 def _phase2_gold(args, dataset, data_plot, closing_plots):
     """GOLD alone: the phase-1 pair goes on training on the uniform loader with the discriminator loss re-weighted from
     --p1_step on.  No logit file, no scores, no D_drs.  `data_plot`: file name of the opening batch plot under --pictures."""
-    run = _Run(args)
+    run = _run(args)
     _single_process_pictures(args, run)
-    baseline = Path(f'{args.work_dir}/{args.baseline_exp_name}')
+    start = _phase1_files(args)[1]
     netG, netD, optG, optD = get_gan_model(dataset_name=args.dataset, model=args.model, loss_type=args.loss_type, gold=True)
-    start = {net: str(_checkpoint(baseline, net, args.p1_step)) for net in ('netG', 'netD')}
     print_num_params(netG, netD)
-    train_set = get_predefined_dataset(dataset_name=args.dataset, root=args.root, weights=None,
-                                       major_ratio=args.major_ratio, num_data=args.num_data, dataset=dataset)
-    loader = _plain_weighted_loader(train_set, args.batch_size, args.num_workers)
+    loader = _plain_weighted_loader(_dcgan_set(args, dataset), args.batch_size, args.num_workers)
     prefix = args.exp_name.split('/')[-1]
     if args.pictures:                                   # *_phase2_gold.py:103-105 / :106-108, the draw included
         from diagan.utils.plot import plot_data

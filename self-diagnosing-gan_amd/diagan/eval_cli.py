@@ -17,6 +17,7 @@ from pathlib import Path
 import torch
 
 from diagan.cli import _FLAG, make_parser
+from diagan.front_end import Run, sampling_networks, score_logit_record
 
 EVAL_FLAGS = [
     (("--dataset", "-d"), "cifar10", str, None),
@@ -112,49 +113,35 @@ def eval_drs_parser():
     return make_parser(EVAL_FLAGS, DRS_FLAGS)
 
 
+def _setup(args, drs, **model_kwargs):
+    """-> the evaluation drivers' keywords that every script here shares: the run directory, the networks on the device (their
+    checkpoints are restored by the drivers) and, with DRS, its switches.  The caller adds its Inception network."""
+    run = Run(args, no_gpu="evaluation runs on the HIP engine and needs a GPU", no_step="--netG_ckpt_step is required",
+              out_dir=f'{args.work_dir}/{args.exp_name}')
+    netG, netD_drs = sampling_networks(args, args.dataset, drs, run.save_path, run.device, **model_kwargs)
+    common = dict(log_dir=run.save_path, netG=netG, evaluate_step=args.netG_ckpt_step, num_runs=1, device=run.device)
+    if drs:
+        common.update(netD_drs=netD_drs, use_original_netD=args.use_original_netD, is_stylegan2=args.model == 'stylegan2',
+                      visualize=args.pictures)
+    return common
+
+
 def _main(args, drs):
     from diagan.models.inception import InceptionV3
-    from diagan.models.predefined_models import get_gan_model
     from diagan.trainer.evaluate import METRICS, evaluate, evaluate_drs
-    from diagan.utils.settings import set_seed
-    if args.gpu:
-        os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     metrics = [m for m in args.metrics.split(',') if m]
     for m in metrics:
         if m not in METRICS:
             raise SystemExit(f"--metrics: unknown metric {m!r}; choose from {METRICS}")
-    if not args.netG_ckpt_step:
-        raise SystemExit("--netG_ckpt_step is required")
-    if not torch.cuda.is_available():
-        raise SystemExit("evaluation runs on the HIP engine and needs a GPU")
-    save_path = Path(f'{args.work_dir}/{args.exp_name}')
-    save_path.mkdir(parents=True, exist_ok=True)
-    set_seed(args.seed)
-    device = 'cuda'
-
-    print(f'load model from {save_path} step: {args.netG_ckpt_step}')
-    nets = get_gan_model(dataset_name=args.dataset, model=args.model, loss_type=args.loss_type, drs=drs)
-    netG, netD_drs = nets[0], (nets[2] if drs else None)
-    for net in (netG, netD_drs):
-        if net is not None:
-            if not args.netG_train_mode:
-                net.eval()
-            net.to(device)
+    common = _setup(args, drs)
     dataset = 'celeba_64' if args.dataset == 'celeba' else args.dataset
     stats_file = args.stats_file
     if stats_file is None:      # the reference's precomputed file when the user has it; never written under that name from here
         shipped = f'./precalculated_statistics/fid_stats_{_STATS_NAME.get(args.dataset, args.dataset)}.npz'
         stats_file = shipped if os.path.exists(shipped) else None
-    model = InceptionV3(weights=args.fid_weights)
+    common['model'] = InceptionV3(weights=args.fid_weights)
     print(args)
-
-    common = dict(log_dir=save_path, netG=netG, evaluate_step=args.netG_ckpt_step, num_runs=1, device=device, model=model)
-    if drs:
-        run = evaluate_drs
-        common.update(netD_drs=netD_drs, use_original_netD=args.use_original_netD, is_stylegan2=args.model == 'stylegan2',
-                      visualize=args.pictures)
-    else:
-        run = evaluate
+    run = evaluate_drs if drs else evaluate
     for m in metrics:
         if m == 'fid':
             run(metric='fid', dataset=dataset, num_real_samples=args.num_samples, num_fake_samples=args.num_samples,
@@ -215,50 +202,17 @@ def attr_weight_means(sample_weights, attr_index, not_attr_index, train_num=CELE
 
 
 def _sample_weights(run_dir, p1_step, window, resample_score, device):
-    import pickle
-    from diagan.utils.plot import calculate_scores
-    logit_path = Path(run_dir) / 'logits_netD_eval.pkl'
-    print(f'Use logit from: {logit_path}')
-    with open(logit_path, "rb") as f:
-        logits = pickle.load(f)
-    scores = calculate_scores(logits, start_epoch=p1_step - window, end_epoch=p1_step, device=device, keys=[resample_score])
-    w = scores[resample_score]
-    print(f'sample_weights mean: {w.mean()}, var: {w.var()}, max: {w.max()}, min: {w.min()}')
-    return w
+    return score_logit_record(Path(run_dir) / 'logits_netD_eval.pkl', p1_step, window, device, keys=[resample_score],
+                              show=resample_score)[resample_score]
 
 
 def _group_setup(args, drs, **model_kwargs):
-    """What the four by-group evaluation scripts share: the run directory, the networks on the device, the real images and
-    the Inception network."""
+    """What the four by-group evaluation scripts share: _setup, the real images and the Inception network."""
     from diagan.datasets.predefined import get_predefined_dataset
     from diagan.models.inception import InceptionV3
-    from diagan.models.predefined_models import get_gan_model
-    from diagan.utils.settings import set_seed
-    if args.gpu:
-        os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    if not args.netG_ckpt_step:
-        raise SystemExit("--netG_ckpt_step is required")
-    if not torch.cuda.is_available():
-        raise SystemExit("evaluation runs on the HIP engine and needs a GPU")
-    save_path = Path(f'{args.work_dir}/{args.exp_name}')
-    save_path.mkdir(parents=True, exist_ok=True)
-    set_seed(args.seed)
-    device = 'cuda'
-    print(f'load model from {save_path} step: {args.netG_ckpt_step}')
-    nets = get_gan_model(dataset_name=args.dataset, model=args.model, loss_type=args.loss_type, drs=drs, **model_kwargs)
-    netG, netD_drs = nets[0], (nets[2] if drs else None)
-    for net in (netG, netD_drs):
-        if net is not None:
-            if not args.netG_train_mode:
-                net.eval()
-            net.to(device)
-    dataset = get_predefined_dataset(args.dataset, root=args.root, num_data=args.num_data)
-    model = InceptionV3(weights=args.fid_weights)
-    common = dict(log_dir=save_path, netG=netG, dataset=dataset, evaluate_step=args.netG_ckpt_step, num_runs=1, device=device,
-                  model=model)
-    if drs:
-        common.update(netD_drs=netD_drs, use_original_netD=args.use_original_netD, is_stylegan2=args.model == 'stylegan2',
-                      visualize=args.pictures)
+    common = _setup(args, drs, **model_kwargs)
+    common['dataset'] = get_predefined_dataset(args.dataset, root=args.root, num_data=args.num_data)
+    common['model'] = InceptionV3(weights=args.fid_weights)
     return common
 
 

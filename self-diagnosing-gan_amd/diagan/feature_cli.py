@@ -15,8 +15,9 @@ import os
 
 import torch
 
-from diagan.attr_cli import COUNT_FLAGS as _ATTR_COUNT_FLAGS, append_row, load_generator
+from diagan.attr_cli import COUNT_FLAGS as _ATTR_COUNT_FLAGS
 from diagan.cli import make_parser
+from diagan.front_end import Run, append_count_row, count_generated, load_generator
 
 DATASETS = {       # dataset -> (directory name of the checkpoints, channels, the reference's hard-coded root)
     'color_mnist': ('color-mnist', 3, './dataset/colour_mnist'),
@@ -97,16 +98,11 @@ def train(args, dataset_name, num_data=None, epochs=None, size=None, save_dir=No
     object (fetch_range(lo, hi) -> fp32 [b, C, H, W] in [-1, 1], .targets int64 on the device); save_interval is 10 as in the
     reference.  These are for tests and smoke runs."""
     from diagan.models.convnets import SimpleConvNet
-    from diagan.utils.settings import set_seed
     tag, channels, _ = DATASETS[dataset_name]
-    if args.gpu is not None:                     # (tests pass None: the process has its device already)
-        os.environ['CUDA_VISIBLE_DEVICES'] = str(args.gpu)
-    if not torch.cuda.is_available():
-        raise SystemExit("the classifier trains on the HIP engine and needs a GPU")
+    # (--gpu is an int here; tests pass None: the process has its device already)
+    device = Run(args, no_gpu="the classifier trains on the HIP engine and needs a GPU").device
     num_data = args.num_data if num_data is None else num_data
     epochs = args.epochs if epochs is None else epochs
-    set_seed(args.seed)
-    device = 'cuda'
     if dataset is None:
         dataset = _dataset(dataset_name, args.root, num_data, size, args.seed, device)
     model = SimpleConvNet(num_labels=NUM_LABELS, num_channels=channels).to(device)
@@ -160,21 +156,12 @@ def count(args, classifier=None):
         model.load_state_dict(torch.load(args.classifier_ckpt, map_location='cpu', weights_only=True))
     model.to(device).eval()
 
-    batch_size = min(args.batch_size, args.num_samples)
-    num_batches = args.num_samples // batch_size
-    model.histogram().zero_()
-    for _ in range(num_batches):
-        with torch.no_grad():
-            model.count(netG.generate_images(batch_size, device=device).float().contiguous())
-    row = count_row(args.dataset, model.histogram().tolist())        # the one read
+    row = count_row(args.dataset, count_generated(args, netG, model, model.histogram(), device)[0])
     major, minor, other = row[1:]
     print(f'major: {major}')
     print(f'minor: {minor}')
     print(f'other: {other}')
-
-    output_dir = os.path.join(save_path, 'evaluate', f'step-{step}')
-    os.makedirs(output_dir, exist_ok=True)
-    append_row(os.path.join(output_dir, 'count_group.csv'), COUNT_CSV_HEADER, row)
+    append_count_row(save_path, step, 'count_group.csv', COUNT_CSV_HEADER, row)
     return major, minor, other
 
 

@@ -155,7 +155,7 @@ def test_two_rank_mnist_dcgan_step_equals_microbatch_emulation(tmp_path):
 
 
 def _worker_rank_noise(rank, world, port, out_dir):
-    """The CLI's data-parallel start (diagan/cli.py::_Run.replicate): same seed everywhere, broadcast, then per-rank DEVICE
+    """The CLI's data-parallel start (diagan/front_end.py::Run.replicate): same seed everywhere, broadcast, then per-rank DEVICE
     seeds; noise is drawn by the networks themselves (no injection).  Phase-2 shape: D's all-reduce is left in flight
     under the D_drs update (LogTrainer._updates)."""
     import sys
